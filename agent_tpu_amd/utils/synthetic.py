@@ -39,16 +39,23 @@ def make_text_rows(n: int, words_per_row: int = 150, seed: int = 0):
     return out
 
 
-def write_csv(path: str, n: int, words_per_row: int = 150, seed: int = 0, quote_every: int = 7) -> str:
-    """Write ``n`` rows; every ``quote_every``-th text is quoted with an embedded comma/quote/newline."""
+def write_csv(path: str, n: int, words_per_row: int = 150, seed: int = 0, quote_every: int = 7,
+              unique_rows: Optional[int] = None) -> str:
+    """Write ``n`` rows; every ``quote_every``-th text is quoted with an embedded comma/quote/newline.
+
+    With ``unique_rows`` < ``n`` only that many texts are generated and the file repeats them
+    in order (a long file at a bounded generation cost); the first ``unique_rows`` rows are
+    the same either way."""
     import csv
 
-    rows = make_text_rows(n, words_per_row, seed)
+    u = n if unique_rows is None else max(1, min(n, int(unique_rows)))
+    rows = make_text_rows(u, words_per_row, seed)
     tmp = f"{path}.tmp{os.getpid()}"
     with open(tmp, "w", encoding="utf-8", newline="") as f:
         w = csv.writer(f, lineterminator="\n")  # excel dialect, QUOTE_MINIMAL
         w.writerow(["id", "text", "risk"])
-        for i, t in enumerate(rows):
+        for i in range(n):
+            t = rows[i % u]
             if quote_every and i % quote_every == 3:
                 t = t + ', said "x"\nend'
             w.writerow([i, t, (i % 1000) / 1000.0])

@@ -14,6 +14,11 @@ A "step" = one batch of ``--batch-rows`` rows per GPU (S=128 tokens each,
 random-init weights broadcast from rank 0 with RCCL, C1). W warmup steps,
 then exactly K timed steps bracketed by barrier + synchronize; the time is the
 max over ranks. Weak scaling: per-GPU work is fixed as N grows.
+
+A plain run does only that: set up, warm up, time the K steps, print one JSON line.
+``--dump-outputs DIR`` also writes the last timed step's top-k as ``.npy`` (inputs and
+weights are seeded, so two builds can be compared output for output); ``--full`` is
+where measurements that need runs of their own belong.
 """
 from __future__ import annotations
 
@@ -39,6 +44,8 @@ METRIC = "classified rows/sec (whole node) map_classify BERT-base at 1/2/4/8 MI3
 # BASELINE.md / SURVEY.md §6 reference-compute proxies at S=128, batch 32:
 # B9 BERT-base 35.2 rows/s, B10 BERT-large 8.2 rows/s
 BASELINE_ROWS_PER_SEC = {"bert-base": 35.2, "bert-large": 8.2}
+# distinct batches of synthetic text per rank; a run of more steps repeats them (see main)
+UNIQUE_BATCHES = 32
 
 
 def parse():
@@ -62,6 +69,12 @@ def parse():
     ap.add_argument("--dist-backend", default=os.environ.get("BENCH_DIST_BACKEND", "nccl"))
     ap.add_argument("--comm", default=os.environ.get("ATPU_COMM", "torch"), choices=["torch", "native"],
                     help="data-plane collectives: torch.distributed (ProcessGroupNCCL) or the native RcclComm")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's top-k (every rank's rows, rank order) "
+                         "as DIR/topk_idx.npy and DIR/topk_score.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure; the headline needs no run of "
+                         "its own for any of them yet, so today this adds nothing")
     a = ap.parse_args()
     os.environ["ATPU_COMM"] = a.comm
     if a.batch_rows <= 0:
@@ -94,6 +107,17 @@ def launch_ranks(a) -> int:
     out.setdefault("config", {})["launcher"] = "self (bench.py -> child torch.distributed.run)"
     print(json.dumps(out), flush=True)
     return 0
+
+
+def dump_last_step(out_dir: str, idx: torch.Tensor, score: torch.Tensor, world: int, B: int) -> None:
+    """``--dump-outputs``: the top-k labels and probabilities of the last timed step, as the
+    caller of the timed path holds them (every rank's last ``B`` rows, in rank order)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("topk_idx", idx), ("topk_score", score)):
+        last = t.reshape(world, -1, t.shape[-1])[:, -B:].reshape(-1, t.shape[-1])
+        np.save(os.path.join(out_dir, name + ".npy"), last.to(torch.float32).cpu().numpy())
 
 
 def main() -> int:
@@ -134,9 +158,13 @@ def main() -> int:
     cfg = config_for(a.model, num_labels=a.num_labels)
     B = a.batch_rows
     rows_needed = (a.warmup + a.steps) * B
-    csv_path = a.csv or f"/tmp/atpu_bench_r{rank}_{rows_needed}_{a.words_per_row}.csv"
+    # generating a row costs ~0.2 ms of host time, so a long run repeats the first UNIQUE_BATCHES
+    # batches of texts; up to that many batches the file is the fully random one, byte for byte
+    unique = UNIQUE_BATCHES * B
+    tiled = f"_u{unique}" if rows_needed > unique else ""
+    csv_path = a.csv or f"/tmp/atpu_bench_r{rank}_{rows_needed}_{a.words_per_row}{tiled}.csv"
     if not os.path.exists(csv_path):
-        write_csv(csv_path, rows_needed, a.words_per_row, seed=1234 + rank)
+        write_csv(csv_path, rows_needed, a.words_per_row, seed=1234 + rank, unique_rows=unique)
     table = nat.CsvTable(csv_path)
     col = table.column_index("text")
 
@@ -202,6 +230,8 @@ def main() -> int:
     total_rows = world * B * a.steps
     assert idx.shape[0] == total_rows, (idx.shape, total_rows)
     value = total_rows / elapsed
+    if rank == 0 and a.dump_outputs:
+        dump_last_step(a.dump_outputs, idx, score, world, B)
     if rank == 0:
         cls_only = eng.model.cls_only_last
         flops = cfg.flops_per_row_executed(a.seq_len, cls_only) * total_rows / elapsed
