@@ -184,6 +184,16 @@ PYBIND11_MODULE(_atpu, m) {
   m.attr("EPI_RESIDUAL") = static_cast<int>(kEpiResidual);
   m.attr("EPI_RELU") = static_cast<int>(kEpiRelu);
   m.attr("EPI_OUT_F32") = static_cast<int>(kEpiOutF32);
+  m.def(
+      "cls_attend",
+      [](uintptr_t g, uintptr_t fin, uintptr_t U, uintptr_t lens, uintptr_t Z, int B, int seq, int H, int heads,
+         uintptr_t stream) {
+        cls_attend(P<const bf16>(g), P<const float>(fin), P<const bf16>(U), P<const int32_t>(lens), P<bf16>(Z), B, seq,
+                   H, heads, S(stream));
+      },
+      "[CLS] attention over raw hidden rows (K / V projection re-associated into U and the out-projection)",
+      py::arg("g"), py::arg("fin"), py::arg("U"), py::arg("lens"), py::arg("Z"), py::arg("B"), py::arg("S"),
+      py::arg("H"), py::arg("heads"), py::arg("stream"));
   m.def("decode_attention", [](uintptr_t q, int ldq, uintptr_t k, uintptr_t v, int ldkv, int seq_stride, int group,
                                uintptr_t lens, uintptr_t step_dev, uintptr_t hist, int hist_stride, uintptr_t bias,
                                int bias_stride, uintptr_t out, int ldo, int rows, int H, float scale, uintptr_t stream,

@@ -105,6 +105,12 @@ void gemm256h(const GemmArgs& g, int mode, hipStream_t stream);
 // Bt = the QKV weight with rows in [head][Q 64 | K 64 | V 64] order (bias / colsum likewise),
 // g.C = the context [M, N / 3] (row stride g.ldc), lens[M / 128] the sequence lengths
 void qkv_attention(const GemmArgs& g, const int32_t* lens, float scale, hipStream_t stream);
+// [CLS] attention of the last BERT layer without a K / V projection (cls_attend.hip): g [B*128, H]
+// raw hidden rows, fin [B*128, 2] their (rstd, rstd*mu), U [B, heads*H] one projected query per
+// head, Z [B, heads*H] = sum_j p_hj LN0(g_j) (LN0: no gamma / beta). S = 128, H % 256 == 0,
+// H <= 1024, heads = H / 64 <= 16; lens clamped to [1, 128]
+void cls_attend(const bf16* g, const float* fin, const bf16* U, const int32_t* lens, bf16* Z, int B, int S, int H,
+                int heads, hipStream_t stream);
 int attention_persist_mode(int set);  // packed BERT attention: 1 persistent (default), 0 per-item
 int num_cus();                        // CUs a persistent grid is sized for (device count, or the budget below)
 int cu_budget(int set);               // >0: size persistent grids for this many CUs (CU-masked streams)

@@ -52,13 +52,25 @@ class BertConfig:
         head = H * H + H + self.num_labels * H + self.num_labels
         return emb + L * layer + head
 
-    def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True) -> float:
-        """FLOPs actually executed per row when the last layer runs on [CLS] only."""
+    def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True,
+                               cls_reassoc: Optional[bool] = None) -> float:
+        """FLOPs actually executed per row when the last layer runs on [CLS] only.
+
+        ``cls_reassoc`` (default: what :class:`BertClassifier` selects on the GPU for this
+        shape): no K/V projection in that layer, but two GEMMs against the derived
+        ``[heads*H, H]`` weights and the [CLS] attention over the raw rows."""
         if not cls_only_last:
             return self.flops_per_row(seq_len)
         H, I, S = self.hidden, self.intermediate, seq_len
+        if cls_reassoc is None:
+            cls_reassoc = (os.getenv("ATPU_CLS_REASSOC", "1") not in ("0", "false", "no")
+                           and os.getenv("ATPU_LN_FOLD", "1") not in ("0", "false", "no")
+                           and self.layers >= 2 and ops.cls_attend_ok(S, H, self.heads))
         full_layer = 2 * S * (4 * H * H + 2 * H * I) + 4 * S * S * H
-        last = 2 * S * 2 * H * H + 2 * (2 * H * H + 2 * H * I) + 4 * S * H
+        if cls_reassoc:
+            last = 2 * (2 * self.heads * H * H) + 4 * S * self.heads * H + 2 * (2 * H * I)
+        else:
+            last = 2 * S * 2 * H * H + 2 * (2 * H * H + 2 * H * I) + 4 * S * H
         return self.flops_per_row(seq_len) - full_layer + last
 
     def flops_per_row(self, seq_len: int) -> float:
@@ -195,6 +207,11 @@ class BertClassifier:
         # QKV projection + attention fused into one kernel (S = 128, LN-folded encoder):
         # ATPU_QKV_ATTN=0 runs the QKV GEMM and the packed attention kernel separately
         self.fused_qkv_attention = os.getenv("ATPU_QKV_ATTN", "1") not in ("0", "false", "no")
+        # [CLS]-only last layer (S = 128, LN-folded encoder) without the all-token K/V projection:
+        # the projection re-associated onto the query and the out-projection (ops/cls_attend.py);
+        # ATPU_CLS_REASSOC=0 projects K/V for every token and runs _cls_layer
+        self.cls_reassoc = (self.ln_fold and os.getenv("ATPU_CLS_REASSOC", "1") not in ("0", "false", "no")
+                            and ops.cls_attend_ok(128, cfg.hidden, cfg.heads))
 
     # ------------------------------------------------------------ LN folding
     def folded(self) -> Dict[str, torch.Tensor]:
@@ -224,6 +241,10 @@ class BertClassifier:
                 f[q + "qkv_bh"] = src[q + "qkv_b"][perm].float().contiguous()
                 if i > 0:
                     f[q + "qkv_ch"] = f[q + "qkv_c"][perm].contiguous()
+            if self.cls_reassoc and self.cfg.layers >= 2:
+                q, ln2 = f"l{self.cfg.layers - 1}.", f"l{self.cfg.layers - 2}."
+                f.update(ops.cls_reassoc_weights(p[q + "qkv_w"], p[q + "qkv_b"], p[q + "o_w"], p[q + "o_b"],
+                                                 p[ln2 + "ln2_g"], p[ln2 + "ln2_b"], self.cfg.heads))
             self._folded = f
         return self._folded
 
@@ -280,8 +301,15 @@ class BertClassifier:
             return ops.layernorm(g, p[ln2 + "ln2_g"], p[ln2 + "ln2_b"], eps)
         # last layer on the [CLS] rows (see encode): K/V over every token from the raw g
         q = f"l{cfg.layers - 1}."
-        kv = ops.linear_ln(g, f[q + "qkv_w"][H:], f[q + "qkv_b"][H:], in_fin=fin, colsum=f[q + "qkv_c"][H:])
         h_cls = ops.layernorm(g.view(B, S, H)[:, 0, :].contiguous(), p[ln2 + "ln2_g"], p[ln2 + "ln2_b"], eps)
+        if self.cls_reassoc and S == 128 and "cls_wu" in f:
+            # no K/V projection: one projected query per head against the raw rows, the value
+            # and out-projection as one GEMM over the [B, heads*H] context (ops/cls_attend.py)
+            u = ops.linear(h_cls, f["cls_wu"], f["cls_bu"])
+            z = ops.cls_attend(g, fin, u, lens, cfg.heads)
+            h1 = ops.linear(z, f["cls_wz"], f["cls_bz"], residual=h_cls)
+            return self._cls_ffn(h1)
+        kv = ops.linear_ln(g, f[q + "qkv_w"][H:], f[q + "qkv_b"][H:], in_fin=fin, colsum=f[q + "qkv_c"][H:])
         return self._cls_layer(h_cls, kv, lens, B, S)
 
     def _cls_layer(self, h_cls: torch.Tensor, kv: torch.Tensor, lens: torch.Tensor, B: int, S: int) -> torch.Tensor:
@@ -292,6 +320,12 @@ class BertClassifier:
         ctx = ops.decode_attention(qc, kv[:, :H], kv[:, H:], cfg.heads, S, 1, lens=lens,
                                    scale=1.0 / math.sqrt(cfg.head_dim))
         h1 = ops.linear(ctx, p[q + "o_w"], p[q + "o_b"], residual=h_cls.contiguous())
+        return self._cls_ffn(h1)
+
+    def _cls_ffn(self, h1: torch.Tensor) -> torch.Tensor:
+        """LN1, FFN and LN2 of the last layer on the [CLS] rows' attention output + residual."""
+        cfg, p = self.cfg, self.p
+        q = f"l{cfg.layers - 1}."
         h1 = ops.layernorm(h1, p[q + "ln1_g"], p[q + "ln1_b"], cfg.eps)
         f = ops.linear(h1, p[q + "f1_w"], p[q + "f1_b"], act="gelu")
         h2 = ops.linear(f, p[q + "f2_w"], p[q + "f2_b"], residual=h1)

@@ -13,6 +13,7 @@ from .decode import DecEmbed, decode_advance, decode_advance_ok  # noqa: F401
 from .decode import beam_select, beam_select_ref, ngram_bans, lm_head_topk, lm_head, LmHead, LM_HEAD_MAX_K  # noqa: F401
 from .attention import attention_packed, attention  # noqa: F401
 from .qkv_attention import qkv_attention, qkv_attention_ok, qkv_head_order  # noqa: F401
+from .cls_attend import cls_attend, cls_attend_ok, cls_attend_ref, cls_reassoc_weights  # noqa: F401
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
