@@ -105,6 +105,32 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("in_fin"), py::arg("colsum"),
       py::arg("res_fin"), py::arg("gamma"), py::arg("part_out"), py::arg("stream"));
   m.def(
+      "gemm_i8",
+      [](uintptr_t A, int lda, uintptr_t a_scale, uintptr_t Bt, int ldb, uintptr_t b_scale, uintptr_t C, int ldc,
+         uintptr_t bias, uintptr_t R, int ldr, int M, int N, int K, int epi, uintptr_t acc_out, int ldacc,
+         uintptr_t stream) {
+        GemmI8Args g;
+        g.A = P<const int8_t>(A); g.lda = lda; g.a_scale = P<const float>(a_scale);
+        g.Bt = P<const int8_t>(Bt); g.ldb = ldb; g.b_scale = P<const float>(b_scale);
+        g.C = P<bf16>(C); g.ldc = ldc; g.bias = P<const float>(bias); g.R = P<const bf16>(R); g.ldr = ldr;
+        g.M = M; g.N = N; g.K = K; g.epi = epi; g.acc_out = P<int32_t>(acc_out); g.ldacc = ldacc;
+        gemm_i8(g, S(stream));
+      },
+      "int8 MFMA GEMM C = epi(float(A @ Bt^T) * a_scale * b_scale); acc_out: raw int32 accumulators only",
+      py::arg("A"), py::arg("lda"), py::arg("a_scale"), py::arg("Bt"), py::arg("ldb"), py::arg("b_scale"), py::arg("C"),
+      py::arg("ldc"), py::arg("bias"), py::arg("R"), py::arg("ldr"), py::arg("M"), py::arg("N"), py::arg("K"),
+      py::arg("epi"), py::arg("acc_out"), py::arg("ldacc"), py::arg("stream"));
+  m.def("gemm_i8_ok", &gemm_i8_ok, py::arg("M"), py::arg("N"), py::arg("K"), "shapes gemm_i8 takes");
+  m.def("quantize_rows_i8", [](uintptr_t x, int ldx, uintptr_t q, int ldq, uintptr_t scale, int rows, int K,
+                               uintptr_t stream) {
+    quantize_rows_i8(P<const bf16>(x), ldx, P<int8_t>(q), ldq, P<float>(scale), rows, K, S(stream));
+  });
+  m.def("layernorm_quant_i8", [](uintptr_t x, uintptr_t res, uintptr_t g, uintptr_t b, uintptr_t out, uintptr_t q,
+                                 uintptr_t scale, int rows, int N, float eps, uintptr_t stream) {
+    layernorm_quant_i8(P<const bf16>(x), P<const bf16>(res), P<const float>(g), P<const float>(b), P<bf16>(out),
+                       P<int8_t>(q), P<float>(scale), rows, N, eps, S(stream));
+  });
+  m.def(
       "gemm256h",
       [](uintptr_t A, int lda, uintptr_t Bt, int ldb, uintptr_t C, int ldc, uintptr_t bias, int M, int N, int K,
          int epi, uintptr_t in_fin, uintptr_t colsum, int mode, uintptr_t stream) {

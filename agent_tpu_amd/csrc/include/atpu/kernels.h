@@ -111,6 +111,43 @@ void qkv_attention(const GemmArgs& g, const int32_t* lens, float scale, hipStrea
 // H <= 1024, heads = H / 64 <= 16; lens clamped to [1, 128]
 void cls_attend(const bf16* g, const float* fin, const bf16* U, const int32_t* lens, bf16* Z, int B, int S, int H,
                 int heads, hipStream_t stream);
+
+// ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
+// Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),
+// q[r][k] = clamp(rint(x[r][k] * (127 / amax_r)), -127, 127). One wave per row; K % 16 == 0,
+// 16-B aligned x rows, 8-B aligned q rows. Weights [N, K] go through the same kernel (per
+// output channel). Inf / NaN inputs are unspecified.
+void quantize_rows_i8(const bf16* x, int ldx, int8_t* q, int ldq, float* scale, int rows, int K,
+                      hipStream_t stream);
+struct GemmI8Args {
+  const int8_t* A = nullptr;  // [M, K] row-major, leading dim lda (bytes)
+  int lda = 0;
+  const float* a_scale = nullptr;  // [M]
+  const int8_t* Bt = nullptr;      // [N, K] row-major
+  int ldb = 0;
+  const float* b_scale = nullptr;  // [N]
+  bf16* C = nullptr;               // [M, N], leading dim ldc
+  int ldc = 0;
+  const float* bias = nullptr;  // [N] fp32
+  const bf16* R = nullptr;      // residual [M, N], leading dim ldr
+  int ldr = 0;
+  int M = 0, N = 0, K = 0;
+  int epi = 0;  // kEpiBias | kEpiGelu | kEpiResidual
+  // when set: write the raw int32 accumulators [M, N] (leading dim ldacc) and nothing else
+  int32_t* acc_out = nullptr;
+  int ldacc = 0;
+};
+// C = bf16(gelu?(float(A . Bt^T) * a_scale[m] * b_scale[n] + bias[n]) + R[m][n]), int32 accumulation
+// on v_mfma_i32_16x16x64_i8 (exact). One 128x128 kernel for every M, no split-K: a row's result
+// does not depend on M or on the tile it lands in.
+void gemm_i8(const GemmI8Args& g, hipStream_t stream);
+// shapes gemm_i8 takes: M >= 1, N % 16 == 0, K % 64 == 0, K <= 2^17
+bool gemm_i8_ok(int M, int N, int K);
+// layernorm_bf16 with a second output: the bf16 row and its quantisation (q, scale), bit for
+// bit quantize_rows_i8 of the bf16 output, in one pass over the row
+void layernorm_quant_i8(const bf16* x, const bf16* res, const float* gamma, const float* beta, bf16* out, int8_t* q,
+                        float* scale, int rows, int N, float eps, hipStream_t stream);
+
 int attention_persist_mode(int set);  // packed BERT attention: 1 persistent (default), 0 per-item
 int num_cus();                        // CUs a persistent grid is sized for (device count, or the budget below)
 int cu_budget(int set);               // >0: size persistent grids for this many CUs (CU-masked streams)

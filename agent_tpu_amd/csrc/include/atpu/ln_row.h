@@ -3,6 +3,7 @@
 #pragma once
 
 #include "atpu/common.h"
+#include "atpu/quant_i8.h"
 
 namespace atpu {
 
@@ -18,10 +19,13 @@ __device__ __forceinline__ float half_sum(float v) {
 // Half the memory instructions of layernorm_kernel for the same bytes; the
 // statistics stay fp32 two-pass, reduced over the half wave.
 // one row of the half-wave LayerNorm: LN(x_row (+ res_row)) -> out_row (rows of N = 256 NG)
-template <int NG, bool NTL>
+// QUANT: also the int8 quantisation of the bf16 output row (qrow, *scale_out), the arithmetic of
+// quantize_rows_i8 on the values just rounded; call it with both half-waves' lanes active.
+template <int NG, bool NTL, bool QUANT = false>
 __device__ __forceinline__ void ln_hw_row(const bf16* __restrict__ xrow, const bf16* __restrict__ rrow,
                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                          bf16* __restrict__ orow_base, bool live, float eps, int hl) {
+                                          bf16* __restrict__ orow_base, bool live, float eps, int hl,
+                                          int8_t* __restrict__ qrow = nullptr, float* __restrict__ scale_out = nullptr) {
   constexpr int N = NG * 256;
   const bf16* xr = xrow + hl * 8;
   float v[NG * 8];
@@ -58,8 +62,12 @@ __device__ __forceinline__ void ln_hw_row(const bf16* __restrict__ xrow, const b
     q += d * d;
   }
   const float rstd = rsqrtf(half_sum(q) * (1.0f / N) + eps);
-  if (!live) return;
+  if constexpr (!QUANT) {
+    if (!live) return;
+  }
   bf16* orow = orow_base + hl * 8;
+  bf16x8 ov[QUANT ? NG : 1];
+  float amax = 0.f;
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int c = g * 256 + hl * 8;
@@ -73,7 +81,23 @@ __device__ __forceinline__ void ln_hw_row(const bf16* __restrict__ xrow, const b
       o[e] = f2bf((v[g * 8 + e] - mean) * rstd * g0[e] + b0[e]);
       o[e + 4] = f2bf((v[g * 8 + e + 4] - mean) * rstd * g1[e] + b1[e]);
     }
-    *reinterpret_cast<bf16x8*>(orow + g * 256) = o;
+    if constexpr (QUANT) {
+      ov[g] = o;
+      amax = absmax_bf16x8(o, amax);
+      if (live) *reinterpret_cast<bf16x8*>(orow + g * 256) = o;
+    } else {
+      *reinterpret_cast<bf16x8*>(orow + g * 256) = o;
+    }
+  }
+  if constexpr (QUANT) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if (!live) return;
+    const float2 si = quant_scale_inv(amax);
+    if (hl == 0) *scale_out = si.x;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) *reinterpret_cast<u32x2*>(qrow + g * 256 + hl * 8) = quant_pack8(ov[g], si.y);
   }
 }
 

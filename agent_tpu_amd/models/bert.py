@@ -181,15 +181,35 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPac
     return pack
 
 
+def resolve_quant(quant: Optional[str]) -> str:
+    """Canonical quantisation mode, ``"none"`` or ``"int8"``; ``None`` reads env ``CLASSIFY_QUANT``
+    (unset, ``""`` or ``none``: off)."""
+    v = os.getenv("CLASSIFY_QUANT", "") if quant is None else quant
+    v = str(v).strip().lower()
+    if v in ("", "none"):
+        return "none"
+    if v == "int8":
+        return "int8"
+    raise ValueError(f"unknown quant {v!r}; known: none, int8")
+
+
 class BertClassifier:
     """Encoder + pooler + classifier over a :class:`ParamPack`.
 
     ``params`` may live on a ROCm device (native kernels) or on the CPU (the
     PyTorch reference path of every op; pass ``fp32=True`` for an fp32 oracle).
+
+    ``quant="int8"`` (default: env ``CLASSIFY_QUANT``): the encoder GEMMs over all ``B*S`` rows (QKV,
+    out-projection, FFN1, FFN2, the K/V projection of a [CLS]-only last layer) run W8A8 on the i8
+    MFMA (``ops/linear_i8.py``: per-row activation scales, per-output-channel weight scales), on
+    the unfolded encoder structure; everything else stays bf16.
     """
 
-    def __init__(self, cfg: BertConfig, pack: ParamPack, fp32: bool = False, cls_only_last: Optional[bool] = None):
+    def __init__(self, cfg: BertConfig, pack: ParamPack, fp32: bool = False, cls_only_last: Optional[bool] = None,
+                 quant: Optional[str] = None):
         self.cfg = cfg
+        self.quant: Optional[str] = "int8" if resolve_quant(quant) == "int8" else None
+        self._quantized: Optional[Dict[str, torch.Tensor]] = None
         self.pack = pack
         self.p = pack.with_dtype(torch.float32) if fp32 else {n: pack[n] for n in pack.names()}
         self.device = pack.buffer.device
@@ -250,6 +270,8 @@ class BertClassifier:
 
     def can_fold(self, B: int, S: int) -> bool:
         M, H, I = B * S, self.cfg.hidden, self.cfg.intermediate
+        if self.quant:  # the int8 GEMM has no LayerNorm-folding epilogues: the unfolded structure
+            return False
         return (self.ln_fold and self.cfg.layers >= 2 and ops.fold_ok(M, 3 * H, H) and ops.fold_ok(M, I, H)
                 and ops.fold_ok(M, H, I))
 
@@ -331,11 +353,67 @@ class BertClassifier:
         h2 = ops.linear(f, p[q + "f2_w"], p[q + "f2_b"], residual=h1)
         return ops.layernorm(h2, p[q + "ln2_g"], p[q + "ln2_b"], cfg.eps)
 
+    # ------------------------------------------------------------ INT8 encoder GEMMs
+    _QUANT_WEIGHTS = ("qkv", "o", "f1", "f2")
+
+    def quantized(self) -> Dict[str, torch.Tensor]:
+        """Per-output-channel int8 weights ``l{i}.{w}_q`` and fp32 scales ``l{i}.{w}_s`` of the encoder
+        GEMMs (built once, where the weights live, by the row quantiser the activations use)."""
+        if self._quantized is None:
+            z = {}
+            for i in range(self.cfg.layers):
+                for w in self._QUANT_WEIGHTS:
+                    n = f"l{i}.{w}"
+                    z[n + "_q"], z[n + "_s"] = ops.quantize_rows_i8(self.p[n + "_w"])
+            self._quantized = z
+        return self._quantized
+
+    def _lin8(self, x: torch.Tensor, xq, name: str, rows: slice = slice(None), act: Optional[str] = None,
+              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``ops.linear`` of ``x`` against weight ``name`` (its output rows ``rows``) on the int8 GEMM;
+        ``xq``: the ``(q, scale)`` of ``x`` when a producer already made it. A shape the int8 GEMM
+        does not take stays on the bf16 GEMM."""
+        z, p = self.quantized(), self.p
+        wq, ws, b = z[name + "_q"][rows], z[name + "_s"][rows], p[name + "_b"][rows]
+        if not ops.linear_i8_ok(x.shape[0], wq.shape[0], wq.shape[1]):
+            return ops.linear(x, p[name + "_w"][rows], b, act=act, residual=residual)
+        q, s = xq if xq is not None else ops.quantize_rows_i8(x)
+        return ops.linear_i8(q, s, wq, ws, b, act=act, residual=residual, out_dtype=x.dtype)
+
+    def encode_int8(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
+                    cls_only_last: bool = False) -> torch.Tensor:
+        """:meth:`encode` (the unfolded structure) with the all-token GEMMs on the int8 GEMM. Each
+        LayerNorm also emits the quantised rows its consumer GEMM reads (one pass)."""
+        cfg, p = self.cfg, self.p
+        B, S = ids.shape
+        H = cfg.hidden
+        h = ops.embed_layernorm(ids, p["emb.word"], p["emb.pos"], p["emb.type"], p["emb.ln_g"], p["emb.ln_b"],
+                                cfg.eps, type_ids=type_ids)
+        hq = None
+        last_full = cfg.layers - 1 if cls_only_last else cfg.layers
+        for i in range(last_full):
+            q = f"l{i}."
+            qkv = self._lin8(h, hq, q + "qkv")
+            ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
+            h1 = self._lin8(ctx, None, q + "o", residual=h)
+            h1, *h1q = ops.layernorm_quant_i8(h1, p[q + "ln1_g"], p[q + "ln1_b"], cfg.eps)
+            f = self._lin8(h1, h1q, q + "f1", act="gelu")
+            h2 = self._lin8(f, None, q + "f2", residual=h1)
+            h, *hq = ops.layernorm_quant_i8(h2, p[q + "ln2_g"], p[q + "ln2_b"], cfg.eps)
+        if not cls_only_last:
+            return h
+        q = f"l{cfg.layers - 1}."
+        kv = self._lin8(h, hq, q + "qkv", rows=slice(H, None))
+        h_cls = h.view(B, S, H)[:, 0, :]  # strided view: row stride S*H
+        return self._cls_layer(h_cls, kv, lens, B, S)
+
     def encode(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
                cls_only_last: bool = False) -> torch.Tensor:
         """Hidden states ``[B*S, H]``, or ``[B, H]`` [CLS] states with ``cls_only_last``."""
         cfg, p = self.cfg, self.p
         B, S = ids.shape
+        if self.quant:
+            return self.encode_int8(ids, lens, type_ids, cls_only_last)
         if ids.is_cuda and self.can_fold(B, S):
             return self.encode_folded(ids, lens, type_ids, cls_only_last)
         H = cfg.hidden

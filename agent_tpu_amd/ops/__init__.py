@@ -8,6 +8,8 @@ extension cannot load on a GPU, the call raises.
 from .linear import linear, fold_rms_into_linear, EPI_BIAS, EPI_GELU, EPI_TANH, EPI_RESIDUAL, EPI_RELU  # noqa: F401
 from .linear import linear_ln, fold_ln_into_linear, fold_ok, ln_partials_ref, ln_finalize, row_parts_ref  # noqa: F401
 from .linear import row_totals_parts_ref, batch_invariant, set_batch_invariant  # noqa: F401
+from .linear_i8 import quantize_rows_i8, linear_i8, linear_i8_ok, quantize_rows_i8_ref, linear_i8_ref  # noqa: F401
+from .linear_i8 import layernorm_quant_i8  # noqa: F401
 from .decode import decode_attention, kv_append, gather_rows, beam_topk_rows, beam_reorder_hist, MAX_BANS  # noqa: F401
 from .decode import DecEmbed, decode_advance, decode_advance_ok  # noqa: F401
 from .decode import beam_select, beam_select_ref, ngram_bans, lm_head_topk, lm_head, LmHead, LM_HEAD_MAX_K  # noqa: F401

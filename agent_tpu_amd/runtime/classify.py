@@ -57,11 +57,12 @@ class RunStats:
 class ClassifyEngine:
     def __init__(self, cfg: BertConfig, pack: ParamPack, device: torch.device, batch_rows: int = 512,
                  seq_len: int = 128, topk: int = 5, max_row_bytes: int = DEFAULT_MAX_ROW_BYTES,
-                 use_graph: bool = True, slots: int = 2, concurrent: Optional[bool] = None):
+                 use_graph: bool = True, slots: int = 2, concurrent: Optional[bool] = None,
+                 quant: Optional[str] = None):
         if pack.buffer.device != device:
             pack = pack.to(device)
         self.cfg, self.pack, self.device = cfg, pack, device
-        self.model = BertClassifier(cfg, pack)
+        self.model = BertClassifier(cfg, pack, quant=quant)  # quant None: the CLASSIFY_QUANT default
         self.B, self.S = int(batch_rows), int(seq_len)
         self.k = max(1, min(int(topk), cfg.num_labels))
         self.max_row_bytes = int(max_row_bytes)
@@ -99,6 +100,8 @@ class ClassifyEngine:
             nat.cu_budget(share)
         if device.type == "cuda" and self.model.can_fold(self.B, self.S):
             self.model.folded()  # build the LN-folded weights now, so memory_bytes() counts them
+        if self.model.quant:
+            self.model.quantized()  # likewise the int8 weights (and not inside a graph capture)
         self._graphs: Dict[int, Tuple["torch.cuda.CUDAGraph", Tuple[torch.Tensor, ...]]] = {}
         # stage-timed replay: the same step as three graphs (tokenize | encoder | head) with
         # hipEvents between them, so timing_ms carries device time per stage
@@ -394,6 +397,7 @@ class ClassifyEngine:
         """Resident device bytes: weights, the LayerNorm-folded weight copies once built
         (they are ~45 % of the encoder weights), staging and token buffers."""
         folded = getattr(self.model, "_folded", None) or {}
+        folded = dict(folded, **(getattr(self.model, "_quantized", None) or {}))  # int8 weights + scales
         extra = sum(t.numel() * t.element_size() for t in folded.values())
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))

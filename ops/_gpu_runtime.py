@@ -41,26 +41,28 @@ class ModelSpec:
     batch_rows: int
     seq_len: int
     file: Optional[str] = None
+    quant: Optional[str] = None  # "?quant=int8": INT8 encoder GEMMs; None: the CLASSIFY_QUANT default
 
 
 def parse_spec(path: str) -> ModelSpec:
-    from agent_tpu_amd.models.bert import PRESETS
+    from agent_tpu_amd.models.bert import PRESETS, resolve_quant
 
     u = urlsplit(path)
     q = {k: v[-1] for k, v in parse_qs(u.query).items()}
+    quant = resolve_quant(q["quant"]) if "quant" in q else None  # an unknown value raises ValueError
     base = u.path if u.scheme in ("", "file") else path
     seq = int(q.get("seq", os.getenv("CLASSIFY_SEQ_LEN", "128")))
     batch = int(q.get("batch", os.getenv("CLASSIFY_BATCH_ROWS", "0")) or 0)
     if base in PRESETS:
         return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
-                         int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq)
+                         int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant)
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
         with open(base + ".json") as f:
             meta = json.load(f)
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
-                         file=base)
+                         file=base, quant=quant)
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -145,7 +147,7 @@ def _build_handle(model_path: str, device) -> GpuHandle:
         spec, cfg = box["spec"], box["cfg"]
         batch = spec.batch_rows or _auto_batch_rows(spec.preset, spec.seq_len)
         eng = ClassifyEngine(cfg, pack, device, batch_rows=batch, seq_len=spec.seq_len,
-                             topk=min(cfg.num_labels, 64))
+                             topk=min(cfg.num_labels, 64), quant=spec.quant)
         sync()
         h = GpuHandle(spec, cfg, eng)
         t2 = time.perf_counter()
