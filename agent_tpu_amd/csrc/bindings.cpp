@@ -357,6 +357,15 @@ PYBIND11_MODULE(_atpu, m) {
     tokenize_hash(P<const uint8_t>(text), P<const int32_t>(offsets), P<int32_t>(ids), P<int32_t>(lens), B, Sq, vocab,
                   max_row_bytes, S(stream), text_bytes);
   });
+  m.def("tokenize_wordpiece",
+        [](uintptr_t text, uintptr_t offsets, uintptr_t ids, uintptr_t lens, int B, int Sq, uintptr_t table,
+           py::array_t<int32_t, py::array::c_style> header, long long table_bytes, int max_row_bytes,
+           uintptr_t stream, long long text_bytes) {
+          ATPU_CHECK(header.size() >= 16 && table_bytes >= 64, "tokenize_wordpiece: header must have 16 words");
+          tokenize_wordpiece(P<const uint8_t>(text), P<const int32_t>(offsets), P<int32_t>(ids), P<int32_t>(lens), B,
+                             Sq, P<const uint8_t>(table), header.data(), static_cast<size_t>(table_bytes),
+                             max_row_bytes, S(stream), text_bytes);
+        });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),
@@ -390,6 +399,42 @@ PYBIND11_MODULE(_atpu, m) {
         return py::make_tuple(ids, lens);
       },
       py::arg("text"), py::arg("offsets"), py::arg("seq_len"), py::arg("vocab"), py::arg("max_row_bytes"));
+  m.def(
+      "wordpiece_build_table",
+      [](const std::vector<std::string>& entries, bool lowercase) {
+        std::vector<uint8_t> t;
+        try {
+          t = wordpiece_build_table(entries, lowercase);
+        } catch (const std::invalid_argument& e) {
+          throw py::value_error(e.what());
+        }
+        py::array_t<uint8_t> out(static_cast<py::ssize_t>(t.size()));
+        std::memcpy(out.mutable_data(), t.data(), t.size());
+        return out;
+      },
+      py::arg("entries"), py::arg("lowercase"));
+  m.def(
+      "wordpiece_host",
+      [](py::array_t<uint8_t, py::array::c_style> text, py::array_t<int32_t, py::array::c_style> offsets, int Sq,
+         py::array_t<uint8_t, py::array::c_style> table, int max_row_bytes) {
+        const int B = static_cast<int>(offsets.size()) - 1;
+        ATPU_CHECK(B >= 0, "wordpiece_host: offsets must have B+1 entries");
+        ATPU_CHECK(Sq >= 2, "wordpiece_host: seq_len must be >= 2");
+        const int32_t* o = offsets.data();
+        ATPU_CHECK(o[0] >= 0 && o[B] <= static_cast<int64_t>(text.size()), "wordpiece_host: offsets outside the text");
+        for (int r = 0; r < B; ++r) ATPU_CHECK(o[r] <= o[r + 1], "wordpiece_host: offsets must not decrease");
+        py::array_t<int32_t> ids({B, Sq});
+        py::array_t<int32_t> lens(B);
+        try {
+          py::gil_scoped_release nogil;
+          wordpiece_host(text.data(), o, ids.mutable_data(), lens.mutable_data(), B, Sq, table.data(),
+                         static_cast<size_t>(table.size()), max_row_bytes);
+        } catch (const std::invalid_argument& e) {
+          throw py::value_error(e.what());
+        }
+        return py::make_tuple(ids, lens);
+      },
+      py::arg("text"), py::arg("offsets"), py::arg("seq_len"), py::arg("table"), py::arg("max_row_bytes"));
   m.def(
       "word_maps_host",
       [](py::array_t<uint8_t, py::array::c_style> text, py::array_t<int64_t, py::array::c_style> offsets, int vocab,

@@ -255,6 +255,13 @@ void embed_gather(const int32_t* ids, const bf16* table, bf16* out, int tokens, 
 void tokenize_hash(const uint8_t* text, const int32_t* offsets, int32_t* ids, int32_t* lens, int B, int S,
                    int vocab, int max_row_bytes, hipStream_t stream,
                    long long text_bytes);
+// WordPiece vocabulary tokenizer ("atpu-wordpiece v1"): greedy longest match against the packed
+// table of atpu/wordpiece.h. ``table``: the table on the launch device (16-byte aligned, resident
+// while the kernel runs); ``header``: the host copy of its first 16 words, ``table_bytes`` its
+// size. Output as tokenize_hash, with the special ids of the vocabulary.
+void tokenize_wordpiece(const uint8_t* text, const int32_t* offsets, int32_t* ids, int32_t* lens, int B, int S,
+                        const uint8_t* table, const int32_t* header, size_t table_bytes, int max_row_bytes,
+                        hipStream_t stream, long long text_bytes);
 
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);

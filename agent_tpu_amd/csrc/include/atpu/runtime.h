@@ -19,6 +19,13 @@ namespace atpu {
 // Host twin of the K1 GPU tokenizer (identical output, see tokenize.hip).
 void tokenize_host(const uint8_t* text, const int32_t* offsets, int32_t* ids, int32_t* lens, int B, int S, int vocab,
                    int max_row_bytes);
+// WordPiece vocabulary tokenizer ("atpu-wordpiece v1", runtime/wordpiece.cpp). The packed table
+// (atpu/wordpiece.h) of a vocabulary, entry i being line i of vocab.txt; throws
+// std::invalid_argument when it is empty or lacks [PAD] / [UNK] / [CLS] / [SEP].
+std::vector<uint8_t> wordpiece_build_table(const std::vector<std::string>& entries, bool lowercase);
+// Host twin of the WordPiece kernel on the same table (identical output, see tokenize_wp.hip).
+void wordpiece_host(const uint8_t* text, const int32_t* offsets, int32_t* ids, int32_t* lens, int B, int S,
+                    const uint8_t* table, size_t table_bytes, int max_row_bytes);
 // Per document (words joined by single 0x20 bytes): its distinct hash-token ids, ascending,
 // and the index of the first word producing each (at most cap tokens per word); doc_off[B+1]
 // delimits each document's entries in ids / word_of (detokenization maps, runtime/summarize.py)

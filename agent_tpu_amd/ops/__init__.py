@@ -17,6 +17,6 @@ from .attention import attention_packed, attention  # noqa: F401
 from .qkv_attention import qkv_attention, qkv_attention_ok, qkv_head_order  # noqa: F401
 from .cls_attend import cls_attend, cls_attend_ok, cls_attend_ref, cls_reassoc_weights  # noqa: F401
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
-from .tokenize import tokenize  # noqa: F401
+from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

@@ -30,7 +30,7 @@ from .. import ops
 from .._native import native
 from ..models.bert import BertClassifier, BertConfig
 from ..models.params import ParamPack
-from ..tokenizer import DEFAULT_MAX_ROW_BYTES, pack_rows
+from ..tokenizer import DEFAULT_MAX_ROW_BYTES, WordPieceVocab, pack_rows
 from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
@@ -58,10 +58,18 @@ class ClassifyEngine:
     def __init__(self, cfg: BertConfig, pack: ParamPack, device: torch.device, batch_rows: int = 512,
                  seq_len: int = 128, topk: int = 5, max_row_bytes: int = DEFAULT_MAX_ROW_BYTES,
                  use_graph: bool = True, slots: int = 2, concurrent: Optional[bool] = None,
-                 quant: Optional[str] = None):
+                 quant: Optional[str] = None, vocab: Optional[WordPieceVocab] = None):
         if pack.buffer.device != device:
             pack = pack.to(device)
         self.cfg, self.pack, self.device = cfg, pack, device
+        # a model with a vocabulary: K1 is the WordPiece kernel on its table; None: the hash tokenizer
+        self.vocab = vocab
+        if vocab is not None:
+            if len(vocab) > cfg.vocab_size:
+                raise ValueError(f"{vocab.source}: {len(vocab)} vocabulary entries exceed the model's "
+                                 f"vocab_size {cfg.vocab_size}")
+            if device.type == "cuda":
+                vocab.device_table(device)  # uploaded now: the launches inside a graph capture allocate nothing
         self.model = BertClassifier(cfg, pack, quant=quant)  # quant None: the CLASSIFY_QUANT default
         self.B, self.S = int(batch_rows), int(seq_len)
         self.k = max(1, min(int(topk), cfg.num_labels))
@@ -109,10 +117,18 @@ class ClassifyEngine:
         self._stager = None
 
     # ------------------------------------------------------------ device step
+    def _tokenize(self, text: torch.Tensor, offs: torch.Tensor, ids: Optional[torch.Tensor] = None,
+                  lens: Optional[torch.Tensor] = None, rows: Optional[int] = None):
+        """K1 of this engine: the model's WordPiece vocabulary when it has one, else the hash tokenizer."""
+        if self.vocab is not None:
+            return ops.tokenize_wordpiece(text, offs, self.S, self.vocab, self.max_row_bytes,
+                                          ids=ids, lens=lens, rows=rows)
+        return ops.tokenize(text, offs, self.S, self.cfg.vocab_size, self.max_row_bytes,
+                            ids=ids, lens=lens, rows=rows)
+
     def _step(self, slot: int, rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         ids, lens = self.ids_s[slot], self.lens_s[slot]
-        ops.tokenize(self.text[slot], self.offs[slot], self.S, self.cfg.vocab_size, self.max_row_bytes,
-                     ids=ids, lens=lens, rows=rows)
+        self._tokenize(self.text[slot], self.offs[slot], ids=ids, lens=lens, rows=rows)
         return self.model.forward(ids[:rows], lens[:rows], self.k)
 
     def _graph_step(self, slot: int):
@@ -134,8 +150,7 @@ class ClassifyEngine:
         box = {}
 
         def tok():
-            ops.tokenize(self.text[slot], self.offs[slot], self.S, self.cfg.vocab_size, self.max_row_bytes,
-                         ids=ids, lens=lens, rows=rows)
+            self._tokenize(self.text[slot], self.offs[slot], ids=ids, lens=lens, rows=rows)
 
         def enc():
             box["h"] = self.model.encoder(ids[:rows], lens[:rows])
@@ -225,8 +240,7 @@ class ClassifyEngine:
 
             def fn():
                 if kind == "text":
-                    ops.tokenize(self.text[0], self.offs[0], self.S, self.cfg.vocab_size, self.max_row_bytes,
-                                 ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+                    self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
                 return self.model.forward(ids, lens, self.k)
 
             s = torch.cuda.Stream(self.device)
@@ -244,8 +258,7 @@ class ClassifyEngine:
             g.replay()
         else:
             if kind == "text":
-                ops.tokenize(self.text[0], self.offs[0], self.S, self.cfg.vocab_size, self.max_row_bytes,
-                             ids=self.ids_s[0], lens=self.lens_s[0], rows=bk)
+                self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bk)
             _, idx, sc = self.model.forward(self.ids_s[0][:bk], self.lens_s[0][:bk], self.k)
         both = torch.cat([idx[:m, :k].view(torch.float32), sc[:m, :k]], 1).cpu()  # one D2H, one sync
         return both[:, :k].contiguous().view(torch.int32), both[:, k:].contiguous()
@@ -297,8 +310,7 @@ class ClassifyEngine:
                 idx_all.append(i)
                 sc_all.append(s_)
             else:
-                ids, lens = ops.tokenize(torch.from_numpy(text), torch.from_numpy(offs), self.S,
-                                         self.cfg.vocab_size, self.max_row_bytes)
+                ids, lens = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
                 logits, idx, sc = self.model.forward(ids, lens, k)
                 idx_all.append(idx.cpu())
                 sc_all.append(sc.cpu())
@@ -399,6 +411,8 @@ class ClassifyEngine:
         folded = getattr(self.model, "_folded", None) or {}
         folded = dict(folded, **(getattr(self.model, "_quantized", None) or {}))  # int8 weights + scales
         extra = sum(t.numel() * t.element_size() for t in folded.values())
+        if self.vocab is not None and self.device.type == "cuda":
+            extra += self.vocab.table_bytes  # the WordPiece table on this device
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

@@ -18,10 +18,39 @@ honest choice. Spec:
 
 Three implementations must agree bit-for-bit: :func:`tokenize_rows` (pure
 Python, this file), ``_atpu.tokenize_host`` (C++) and the HIP kernel.
+
+atpu-wordpiece v1 — the tokenizer of a model that comes with a ``vocab.txt``
+(:class:`WordPieceVocab`; host twin ``_atpu.wordpiece_host``, HIP kernel
+``csrc/kernels/tokenize_wp.hip``, again bit-for-bit on any byte string). Spec:
+
+* vocabulary file: one token per line, id = line index, the trailing ``\\n`` /
+  ``\\r\\n`` stripped, the last occurrence of a repeated token wins; ``[PAD]``,
+  ``[UNK]``, ``[CLS]`` and ``[SEP]`` must be present and their ids are read
+  from the file; an entry of more than 4096 bytes cannot match (rows are cut
+  at 4096 bytes at most) and is ignored;
+* byte classes are those of the hash tokenizer: separators, one-byte
+  punctuation words, word bytes (ASCII alnum and every byte >= 0x80); with
+  ``lowercase`` (the default, for uncased models) ASCII ``A-Z`` are folded
+  before matching;
+* each word is matched greedily, longest match first, on bytes: at position
+  ``s`` the longest ``e`` such that bytes ``[s, e)`` are an entry (for
+  ``s > 0``: those bytes prefixed by ``##``); a position that matches nothing
+  makes the whole word one ``[UNK]``, and so does a word of more than 100
+  characters (bytes that are not UTF-8 continuation bytes 0x80-0xBF);
+* ``[CLS]`` + the first ``seq_len - 2`` tokens + ``[SEP]``, then ``[PAD]``;
+  ``len = tokens + 2``; rows are cut at ``max_row_bytes`` first.
+
+Deviations from HF ``BertTokenizer``: no Unicode normalisation (no accent
+stripping, no Unicode lower-casing, no CJK splitting, no Unicode whitespace or
+punctuation classes -- every byte >= 0x80 is a word byte); control bytes
+separate instead of being deleted; a literal special-token string in the text
+(``[SEP]``) is punctuation plus a word. On rows of printable ASCII plus
+``\\t \\n \\r`` without special-token strings the output equals
+``BertTokenizer(vocab_file, do_lower_case=True)`` exactly (tested).
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -102,3 +131,143 @@ def pack_rows(rows: Iterable) -> Tuple[np.ndarray, np.ndarray]:
         offsets[1:] = np.cumsum([len(b) for b in blobs])
     text = np.frombuffer(b"".join(blobs), dtype=np.uint8).copy() if blobs else np.zeros(0, np.uint8)
     return text, offsets
+
+
+# ------------------------------------------------------------ atpu-wordpiece v1
+MAX_WORD_CHARS = 100
+MAX_ENTRY_BYTES = 4096
+SPECIAL_TOKENS = (b"[PAD]", b"[UNK]", b"[CLS]", b"[SEP]")
+_NOT_CONT = bytes(0 if 0x80 <= c <= 0xBF else 1 for c in range(256))
+
+
+class WordPieceVocab:
+    """A BERT ``vocab.txt`` and the three forms it is used in: the dicts of the pure-Python
+    twin (:meth:`tokenize_rows`, the oracle of the other two), the packed host table
+    (:attr:`table`, built once by ``_atpu.wordpiece_build_table``) and its per-device copy
+    (:meth:`device_table`, uploaded once per device)."""
+
+    def __init__(self, entries: Sequence[bytes], lowercase: bool = True, source: str = "<entries>"):
+        self.entries = [bytes(e) for e in entries]
+        self.lowercase = bool(lowercase)
+        self.source = source
+        if not self.entries:
+            raise ValueError(f"{source}: empty vocabulary")
+        self.first: Dict[bytes, int] = {}
+        self.cont: Dict[bytes, int] = {}
+        index: Dict[bytes, int] = {}
+        for i, e in enumerate(self.entries):
+            index[e] = i  # the last occurrence wins
+            is_cont = len(e) > 2 and e.startswith(b"##")
+            piece = e[2:] if is_cont else e
+            if piece and len(piece) <= MAX_ENTRY_BYTES:
+                (self.cont if is_cont else self.first)[piece] = i
+        missing = [s.decode() for s in SPECIAL_TOKENS if s not in index]
+        if missing:
+            raise ValueError(f"{source}: vocabulary has no {', '.join(missing)}")
+        self.pad_id, self.unk_id, self.cls_id, self.sep_id = (index[s] for s in SPECIAL_TOKENS)
+        self.max_len = max([1] + [len(p) for d in (self.first, self.cont) for p in d])
+        self._table: Optional[np.ndarray] = None
+        self._device: Dict[str, object] = {}
+
+    @classmethod
+    def load(cls, path: str, lowercase: bool = True, vocab_size: Optional[int] = None) -> "WordPieceVocab":
+        """Read ``path``; ``vocab_size``: the model's embedding rows, which the ids index."""
+        with open(path, "rb") as f:
+            data = f.read()
+        lines = data.split(b"\n")
+        if lines and lines[-1] == b"":
+            lines.pop()  # the file ends with a newline
+        entries = [ln[:-1] if ln.endswith(b"\r") else ln for ln in lines]
+        if not entries:
+            raise ValueError(f"{path}: empty vocabulary file")
+        if vocab_size is not None and len(entries) > int(vocab_size):
+            raise ValueError(f"{path}: {len(entries)} vocabulary entries exceed the model's vocab_size {vocab_size}")
+        return cls(entries, lowercase, source=str(path))
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    # -------------------------------------------------------------- Python twin
+    def _match(self, word: bytes) -> Optional[List[int]]:
+        out: List[int] = []
+        s, n = 0, len(word)
+        while s < n:
+            d = self.first if s == 0 else self.cont
+            e = min(n, s + self.max_len)
+            hit = None
+            while e > s:
+                hit = d.get(word[s:e])
+                if hit is not None:
+                    break
+                e -= 1
+            if hit is None:
+                return None
+            out.append(hit)
+            s = e
+        return out
+
+    def word_ids(self, word: bytes) -> List[int]:
+        """Ids of one word (word bytes only, or one punctuation byte)."""
+        if len(word) > MAX_WORD_CHARS and sum(word.translate(_NOT_CONT)) > MAX_WORD_CHARS:
+            return [self.unk_id]
+        got = self._match(word.lower() if self.lowercase else word)  # bytes.lower() folds ASCII only
+        return [self.unk_id] if got is None else got
+
+    def token_ids(self, row: bytes, cap: int) -> List[int]:
+        """Token ids of one row (no specials), at most ``cap`` of them."""
+        out: List[int] = []
+        i, n = 0, len(row)
+        while i < n and len(out) < cap:
+            k = _CLASS[row[i]]
+            if k == 0:
+                i += 1
+                continue
+            j = i + 1
+            if k == 2:
+                while j < n and _CLASS[row[j]] == 2:
+                    j += 1
+            out.extend(self.word_ids(row[i:j]))
+            i = j
+        return out[:cap]
+
+    def tokenize_rows(self, rows: Sequence[bytes], seq_len: int,
+                      max_row_bytes: int = DEFAULT_MAX_ROW_BYTES) -> Tuple[np.ndarray, np.ndarray]:
+        """Pure-Python reference: returns ``ids[B, seq_len]`` and ``lens[B]`` (int32)."""
+        ids = np.full((len(rows), seq_len), self.pad_id, dtype=np.int32)
+        lens = np.zeros(len(rows), dtype=np.int32)
+        for r, row in enumerate(rows):
+            toks = self.token_ids(bytes(row[:max_row_bytes]), seq_len - 2)
+            ids[r, 0] = self.cls_id
+            ids[r, 1:1 + len(toks)] = toks
+            ids[r, 1 + len(toks)] = self.sep_id
+            lens[r] = len(toks) + 2
+        return ids, lens
+
+    # ------------------------------------------------------- packed table forms
+    @property
+    def table(self) -> np.ndarray:
+        """The packed table (uint8) that the host twin and the kernel read."""
+        if self._table is None:
+            from ._native import native
+
+            self._table = native().wordpiece_build_table(self.entries, self.lowercase)
+        return self._table
+
+    @property
+    def header(self) -> np.ndarray:
+        return self.table[:64].view(np.int32)
+
+    @property
+    def table_bytes(self) -> int:
+        return int(self.table.size)
+
+    def device_table(self, device):
+        """The table on ``device``: uploaded on first use, then cached (stable pointer)."""
+        import torch
+
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = torch.from_numpy(self.table).to(device)
+            self._device[key] = t
+        return t

@@ -12,6 +12,10 @@ MI355X counterpart of ``/root/reference/ops/_tpu_runtime.py``:
 A "model path" is a BERT preset (``bert-base``, ``bert-large``, ``bert-tiny``),
 optionally with query options ``bert-base?labels=5&seed=3&batch=512``, or a
 ``.safetensors`` file whose config sits next to it as ``<file>.json``.
+``?vocab=/abs/vocab.txt[&lowercase=0]`` (any path) or ``"vocab": "vocab.txt"`` in
+that json (relative to the model file; the query wins) gives the model a WordPiece
+vocabulary: its texts are then tokenized by ``atpu-wordpiece v1`` instead of the
+hash tokenizer.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -42,6 +46,14 @@ class ModelSpec:
     seq_len: int
     file: Optional[str] = None
     quant: Optional[str] = None  # "?quant=int8": INT8 encoder GEMMs; None: the CLASSIFY_QUANT default
+    vocab: Optional[str] = None  # vocab.txt of the model: the WordPiece tokenizer; None: the hash tokenizer
+    lowercase: bool = True  # uncased vocabulary: ASCII A-Z folded before matching
+
+
+def _flag(value: Any) -> bool:
+    if isinstance(value, str):
+        return value.strip().lower() not in ("0", "false", "no", "")
+    return bool(value)
 
 
 def parse_spec(path: str) -> ModelSpec:
@@ -53,16 +65,23 @@ def parse_spec(path: str) -> ModelSpec:
     base = u.path if u.scheme in ("", "file") else path
     seq = int(q.get("seq", os.getenv("CLASSIFY_SEQ_LEN", "128")))
     batch = int(q.get("batch", os.getenv("CLASSIFY_BATCH_ROWS", "0")) or 0)
+    vocab = q.get("vocab") or None
+    lowercase = _flag(q["lowercase"]) if "lowercase" in q else None
     if base in PRESETS:
         return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
-                         int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant)
+                         int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
+                         vocab=vocab, lowercase=True if lowercase is None else lowercase)
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
         with open(base + ".json") as f:
             meta = json.load(f)
+        if vocab is None and meta.get("vocab"):  # the query wins over the json
+            vocab = os.path.join(os.path.dirname(os.path.abspath(base)), str(meta["vocab"]))  # absolute stays
+        if lowercase is None:
+            lowercase = _flag(meta.get("lowercase", True))
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
-                         file=base, quant=quant)
+                         file=base, quant=quant, vocab=vocab, lowercase=lowercase)
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -98,6 +117,26 @@ def _load_host_pack(spec: ModelSpec, cfg):
     return init_random(cfg, seed=spec.seed)
 
 
+def _load_vocab(spec: ModelSpec, cfg):
+    """The model's :class:`WordPieceVocab` with its packed table built, or None (hash tokenizer)."""
+    if not spec.vocab:
+        if spec.file:
+            import logging
+
+            logging.getLogger(__name__).warning(
+                "%s has no vocabulary (\"vocab\" in %s.json or ?vocab=): texts are tokenized by the hash "
+                "tokenizer, whose ids mean nothing to trained weights", spec.file, spec.file)
+        return None
+    from agent_tpu_amd.tokenizer import WordPieceVocab
+
+    try:
+        vocab = WordPieceVocab.load(spec.vocab, lowercase=spec.lowercase, vocab_size=cfg.vocab_size)
+    except OSError as exc:
+        raise FileNotFoundError(f"vocabulary file not readable: {spec.vocab} ({exc})") from None
+    vocab.table  # built here, so a bad file fails the collective load and not the first job
+    return vocab
+
+
 def _build_handle(model_path: str, device) -> GpuHandle:
     """Load a model on this rank, or on every rank of the DP group together.
 
@@ -131,6 +170,9 @@ def _build_handle(model_path: str, device) -> GpuHandle:
         spec = parse_spec(model_path)
         cfg = config_for(spec.preset, num_labels=spec.labels)
         box.update(spec=spec, cfg=cfg)
+        # the vocabulary is read and its table built on every rank (same file, same node: no
+        # broadcast), before the weights, so a missing or bad file on any rank fails the load on all
+        box["vocab"] = _load_vocab(spec, cfg)
         if not spec.file:
             return init_random(cfg, seed=spec.seed, device=device)
         if dist_on and world()[0] != 0:
@@ -147,7 +189,7 @@ def _build_handle(model_path: str, device) -> GpuHandle:
         spec, cfg = box["spec"], box["cfg"]
         batch = spec.batch_rows or _auto_batch_rows(spec.preset, spec.seq_len)
         eng = ClassifyEngine(cfg, pack, device, batch_rows=batch, seq_len=spec.seq_len,
-                             topk=min(cfg.num_labels, 64), quant=spec.quant)
+                             topk=min(cfg.num_labels, 64), quant=spec.quant, vocab=box["vocab"])
         sync()
         h = GpuHandle(spec, cfg, eng)
         t2 = time.perf_counter()
