@@ -220,6 +220,17 @@ PYBIND11_MODULE(_atpu, m) {
       "[CLS] attention over raw hidden rows (K / V projection re-associated into U and the out-projection)",
       py::arg("g"), py::arg("fin"), py::arg("U"), py::arg("lens"), py::arg("Z"), py::arg("B"), py::arg("S"),
       py::arg("H"), py::arg("heads"), py::arg("stream"));
+  m.def(
+      "pool_embed",
+      [](uintptr_t x, uintptr_t fin, uintptr_t gamma, uintptr_t beta, uintptr_t lens, uintptr_t out, int B, int seq,
+         int H, int mode, int normalize, uintptr_t stream) {
+        pool_embed(P<const bf16>(x), P<const float>(fin), P<const float>(gamma), P<const float>(beta),
+                   P<const int32_t>(lens), P<float>(out), B, seq, H, mode, normalize, S(stream));
+      },
+      "sentence embedding: masked mean (mode 0) or row 0 (mode 1) of the hidden rows, the last LayerNorm applied "
+      "to the pooled vector when fin is given (0 = rows already normalised), optional L2 normalisation",
+      py::arg("x"), py::arg("fin"), py::arg("gamma"), py::arg("beta"), py::arg("lens"), py::arg("out"), py::arg("B"),
+      py::arg("S"), py::arg("H"), py::arg("mode"), py::arg("normalize"), py::arg("stream"));
   m.def("decode_attention", [](uintptr_t q, int ldq, uintptr_t k, uintptr_t v, int ldkv, int seq_stride, int group,
                                uintptr_t lens, uintptr_t step_dev, uintptr_t hist, int hist_stride, uintptr_t bias,
                                int bias_stride, uintptr_t out, int ldo, int rows, int H, float scale, uintptr_t stream,

@@ -111,6 +111,14 @@ void qkv_attention(const GemmArgs& g, const int32_t* lens, float scale, hipStrea
 // H <= 1024, heads = H / 64 <= 16; lens clamped to [1, 128]
 void cls_attend(const bf16* g, const float* fin, const bf16* U, const int32_t* lens, bf16* Z, int B, int S, int H,
                 int heads, hipStream_t stream);
+// Sentence embedding (pool_embed.hip): out [B, H] fp32 = the mean over the rows j < len (mode
+// kPoolMean) or row 0 (kPoolCls) of x [B*S, H]. With fin [B*S, 2] = (rstd, rstd*mu), x holds raw
+// rows and the LayerNorm (gamma, beta, both required) is applied to the pooled vector; with
+// fin == nullptr x is already normalised (gamma / beta unused). normalize != 0: out divided by
+// max(||out||_2, 1e-12). S in [1, 512], H % 64 == 0, H in [64, 1024]; lens clamped to [1, S]
+enum PoolMode : int { kPoolMean = 0, kPoolCls = 1 };
+void pool_embed(const bf16* x, const float* fin, const float* gamma, const float* beta, const int32_t* lens,
+                float* out, int B, int S, int H, int mode, int normalize, hipStream_t stream);
 
 // ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
 // Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),

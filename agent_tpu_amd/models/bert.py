@@ -148,8 +148,12 @@ def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: flo
 
 
 def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPack:
-    """Build a pack from a transformers ``BertForSequenceClassification`` state dict."""
+    """Build a pack from a transformers ``BertForSequenceClassification`` state dict, or from a
+    plain ``BertModel`` one (no ``bert.`` prefix, no classifier, the pooler optional): head
+    tensors the dict does not have stay zero."""
     pack = ParamPack(param_specs(cfg))
+    if "embeddings.word_embeddings.weight" in sd and "bert.embeddings.word_embeddings.weight" not in sd:
+        sd = {"bert." + k: v for k, v in sd.items()}
 
     def put(name, t):
         pack[name].copy_(t.to(pack[name].dtype).view(pack[name].shape))
@@ -174,10 +178,10 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPac
         put(f"l{i}.f2_b", sd[b + "output.dense.bias"])
         put(f"l{i}.ln2_g", sd[b + "output.LayerNorm.weight"])
         put(f"l{i}.ln2_b", sd[b + "output.LayerNorm.bias"])
-    put("pool_w", sd["bert.pooler.dense.weight"])
-    put("pool_b", sd["bert.pooler.dense.bias"])
-    put("cls_w", sd["classifier.weight"])
-    put("cls_b", sd["classifier.bias"])
+    for name, key in (("pool_w", "bert.pooler.dense.weight"), ("pool_b", "bert.pooler.dense.bias"),
+                      ("cls_w", "classifier.weight"), ("cls_b", "classifier.bias")):
+        if key in sd:
+            put(name, sd[key])
     return pack
 
 
@@ -232,6 +236,10 @@ class BertClassifier:
         # ATPU_CLS_REASSOC=0 projects K/V for every token and runs _cls_layer
         self.cls_reassoc = (self.ln_fold and os.getenv("ATPU_CLS_REASSOC", "1") not in ("0", "false", "no")
                             and ops.cls_attend_ok(128, cfg.hidden, cfg.heads))
+        # mean-pooled embeddings on the folded encoder: the last LayerNorm applied to the pooled
+        # vector by pool_embed (ops/pool.py); ATPU_EMBED_FUSED=0 finishes every row with
+        # ops.layernorm and pools the normalised rows
+        self.embed_fused = os.getenv("ATPU_EMBED_FUSED", "1") not in ("0", "false", "no")
 
     # ------------------------------------------------------------ LN folding
     def folded(self) -> Dict[str, torch.Tensor]:
@@ -276,7 +284,7 @@ class BertClassifier:
                 and ops.fold_ok(M, H, I))
 
     def encode_folded(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
-                      cls_only_last: bool = False) -> torch.Tensor:
+                      cls_only_last: bool = False, raw: bool = False):
         """:meth:`encode` with every encoder LayerNorm folded into the GEMMs around it.
 
         The post-LN residual stream stays raw (pre-LN sums). The out-proj / FFN2
@@ -284,7 +292,11 @@ class BertClassifier:
         turns them into (rstd, rstd*mu), which FFN1 / the next QKV apply to the
         folded weights' product and FFN2 / the next out-proj apply to their residual.
         Removes 2 LayerNorm passes per layer (each a full read + write of the hidden
-        states); the logits match the unfolded encoder to bf16 rounding."""
+        states); the logits match the unfolded encoder to bf16 rounding.
+
+        ``raw`` (all layers in full only): skip the final LayerNorm and return ``(g, fin, name)``,
+        the last layer's raw rows ``[B*S, H]``, their ``(rstd, rstd*mu)`` and the parameter prefix
+        of the LayerNorm that would finish them (``p[name + "ln2_g"]`` / ``"ln2_b"``)."""
         cfg, p, f = self.cfg, self.p, self.folded()
         B, S = ids.shape
         H, M, eps = cfg.hidden, B * S, cfg.eps
@@ -319,6 +331,9 @@ class BertClassifier:
                               res_gamma=p[q + "ln1_g"], part_out=part)
             ops.ln_finalize(part, H, eps, out=fin)  # LN2 statistics of g
         ln2 = f"l{last_full - 1}."
+        if raw:
+            assert not cls_only_last, "encode_folded: raw rows are those of the full last layer"
+            return g, fin, ln2
         if not cls_only_last:
             return ops.layernorm(g, p[ln2 + "ln2_g"], p[ln2 + "ln2_b"], eps)
         # last layer on the [CLS] rows (see encode): K/V over every token from the raw g
@@ -446,6 +461,28 @@ class BertClassifier:
                 type_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The encoder stage of :meth:`forward` ([CLS] states when the last layer is pruned)."""
         return self.encode(ids, lens, type_ids, cls_only_last=self.cls_only_last and ids.shape[1] > 1)
+
+    def embed(self, ids: torch.Tensor, lens: torch.Tensor, pooling: str = "mean", normalize: bool = True,
+              type_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Sentence embeddings ``[B, H]`` fp32: the mean of the last hidden states over the real
+        tokens (``pooling="mean"``) or the [CLS] state (``"cls"``), L2-normalised with ``normalize``.
+
+        ``mean`` runs every layer in full; on the folded encoder the final LayerNorm is not run
+        over the rows but applied to the pooled vector (:func:`ops.pool_embed` with ``fin``).
+        ``cls`` takes :meth:`encoder`'s output (the pruned, re-associated last layer)."""
+        if pooling not in ("mean", "cls"):
+            raise ValueError("pooling must be 'mean' or 'cls'")
+        B, S = ids.shape
+        p = self.p
+        if pooling == "cls":
+            h = self.encoder(ids, lens, type_ids)  # [B, H] [CLS] states, or every row [B*S, H]
+            return ops.pool_embed(h.contiguous(), lens, B, mode="cls", normalize=normalize)
+        if ids.is_cuda and self.embed_fused and self.can_fold(B, S):
+            g, fin, ln2 = self.encode_folded(ids, lens, type_ids, raw=True)
+            return ops.pool_embed(g, lens, B, fin=fin, gamma=p[ln2 + "ln2_g"], beta=p[ln2 + "ln2_b"],
+                                  normalize=normalize)
+        h = self.encode(ids, lens, type_ids, cls_only_last=False)
+        return ops.pool_embed(h, lens, B, normalize=normalize)
 
     def head(self, h: torch.Tensor, B: int, S: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Pooler + classifier + softmax/top-k (K7) over encoder states ``h``."""

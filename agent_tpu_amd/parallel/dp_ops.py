@@ -325,6 +325,12 @@ def _open_table(path: str):
     return open_csv(path)
 
 
+def _need_head(h) -> None:
+    """map_classify on an encoder-only model (``"head": "none"``): same error on every rank."""
+    if not getattr(h.spec, "head", True):
+        raise ValueError("model has no classifier head")
+
+
 @dp_task("map_classify_csv")
 def classify_csv_task(payload: Dict[str, Any]) -> Any:
     from ops._gpu_runtime import get_gpu_handle, get_model_path  # agent-level registry
@@ -339,6 +345,7 @@ def classify_csv_task(payload: Dict[str, Any]) -> Any:
         timing["cold_load"] = {k: (round(v, 2) if isinstance(v, float) else v) for k, v in h.load_ms.items()}
     err, idx, sc, meta = "", None, None, {}
     try:
+        _need_head(h)
         start = int(payload.get("start_row", 0))
         size = int(payload.get("shard_size", 100))
         if start < 0 or size <= 0:
@@ -394,6 +401,7 @@ def classify_rows_task(payload: Dict[str, Any]) -> Any:
     rank, ws = world()
     h = get_gpu_handle(get_model_path(payload.get("model_path")))
     op, t0 = payload.get("_op", mc.OP_NAME), float(payload.get("_t0", time.time()))
+    _need_head(h)  # the same handle on every rank: all raise together, before any collective
     if "input" in payload:
         return mc.classify_ids(h, payload, op, t0) if rank == 0 else None
     texts = mc.check_texts(payload)  # same payload on every rank: same outcome, no exchange needed
@@ -423,7 +431,110 @@ def classify_batch_task(payload: Dict[str, Any]) -> Any:
     rank, ws = world()
     payloads = payload["payloads"]
     h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    _need_head(h)
     return mc.classify_batch(h, payloads, rank, ws)
+
+
+# ---------------------------------------------------------------- map_embed
+def exchange_errors(exc: Optional[BaseException], extra: Any = None) -> Optional[list]:
+    """:func:`_check_errors` for an op whose errors are its contract (``map_embed``: fixed
+    ``ValueError`` s, no fallback stub): outside a process group the exception itself is raised,
+    with its own type; inside one, the exchange re-raises it typed when every rank agrees."""
+    if exc is not None and not is_dist():
+        raise exc
+    return _check_errors(_err_str(exc) if exc is not None else "", extra)
+
+
+@dp_task("map_embed_rows")
+def embed_rows_task(payload: Dict[str, Any]) -> Any:
+    """``texts`` form of map_embed: rows split over the ranks, embeddings all-gathered (C2)."""
+    from ops import map_embed as me
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    exc, emb = None, None
+    try:
+        opt, texts = me.options(payload), me.check_texts(payload)
+        me.check_json_size(opt, len(texts), h.cfg.hidden)
+        s_r, n_r = split_range(0, len(texts), ws, rank)
+        maybe_inject_fault("embed")
+        emb = h.engine.embed_texts(texts[s_r:s_r + n_r], opt.pooling, opt.normalize).emb
+    except Exception as e:
+        exc = e
+    counts = exchange_errors(exc, int(emb.shape[0]) if emb is not None else 0)
+    (emb,) = all_gather_rows(emb, counts=counts)
+    if rank != 0:
+        return None
+    return me.result(h, emb.cpu(), payload, {"dp_world_size": ws} if ws > 1 else {})
+
+
+@dp_task("map_embed_csv")
+def embed_csv_task(payload: Dict[str, Any]) -> Any:
+    """CSV-shard form of map_embed: the structure of :func:`classify_csv_task` with ``[rows, H]``
+    embeddings in place of the top-k (on a CPU engine the rows are read and embedded as texts)."""
+    from ops import map_embed as me
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    timing: Dict[str, float] = {}
+    with span("load_ms", timing):
+        h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    if getattr(h, "fresh", False):
+        h.fresh = False
+        timing["cold_load"] = {k: (round(v, 2) if isinstance(v, float) else v) for k, v in h.load_ms.items()}
+    exc, emb, meta = None, None, {}
+    try:
+        opt = me.options(payload)
+        start = int(payload.get("start_row", 0))
+        size = int(payload.get("shard_size", 100))
+        if start < 0 or size <= 0:
+            raise ValueError(me.ERRORS["range"])
+        table = _open_table(payload["source_uri"])
+        col = table.native.column_index(str(payload.get("text_column", "text")))
+        if col < 0:
+            raise ValueError(me.ERRORS["column"])
+        total = max(0, min(size, table.num_rows - start))
+        me.check_json_size(opt, total, h.cfg.hidden)
+        s_r, n_r = split_range(start, total, ws, rank)
+        maybe_inject_fault("embed")
+        with span("embed_ms", timing):
+            if h.engine.device.type == "cuda":
+                emb, st = h.engine.embed_table(table.native, s_r, n_r, col, opt.pooling, opt.normalize,
+                                               stage_timing=payload.get("timing", "host") == "device")
+                timing.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.timing_ms.items()})
+            else:
+                fields = (table.native.row(i) for i in range(s_r, s_r + n_r))
+                rows = [f[col] if col < len(f) else "" for f in fields]
+                emb = h.engine.embed_texts(rows, opt.pooling, opt.normalize).emb
+        meta = {"dataset_id": payload.get("dataset_id", "unknown_dataset"), "start_row": start,
+                "end_row": start + total, "dp_world_size": ws}
+    except Exception as e:
+        exc = e
+        if os.getenv("ATPU_DEBUG"):
+            traceback.print_exc()
+    counts = exchange_errors(exc, int(emb.shape[0]) if emb is not None else 0)
+    with span("host_allgather_ms", timing):
+        (emb,) = all_gather_rows(emb, counts=counts)
+    if rank != 0:
+        return None
+    with span("host_d2h_ms", timing):
+        emb_h = emb.cpu()
+    meta["timing_ms"] = timing
+    return me.result(h, emb_h, payload, meta)
+
+
+@dp_task("map_embed_batch")
+def embed_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several ``texts`` jobs of one lease (same model, pooling and normalize): one collective
+    model load, then :func:`ops.map_embed.embed_batch` on every rank."""
+    from ops import map_embed as me
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    payloads = payload["payloads"]
+    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    return me.embed_batch(h, payloads, rank, ws)
 
 
 # ---------------------------------------------------------- risk_accumulate

@@ -43,6 +43,12 @@ class BatchResult:
 
 
 @dataclass
+class EmbedResult:
+    rows: int
+    emb: torch.Tensor    # [rows, H] fp32 (host)
+
+
+@dataclass
 class RunStats:
     rows: int = 0
     batches: int = 0
@@ -115,6 +121,10 @@ class ClassifyEngine:
         # hipEvents between them, so timing_ms carries device time per stage
         self._staged: Dict[int, Tuple[Tuple["torch.cuda.CUDAGraph", ...], Tuple[torch.Tensor, ...]]] = {}
         self._stager = None
+        # embed graphs, keyed by (pooling, normalize): built on first use (an engine that never
+        # embeds allocates nothing for them), from the graph pools of the classify graphs
+        self._egraphs: Dict[Tuple[int, str, bool], Tuple["torch.cuda.CUDAGraph", torch.Tensor]] = {}
+        self._epools: Dict[int, Tuple[int, int]] = {}
 
     # ------------------------------------------------------------ device step
     def _tokenize(self, text: torch.Tensor, offs: torch.Tensor, ids: Optional[torch.Tensor] = None,
@@ -405,6 +415,169 @@ class ClassifyEngine:
         stats.wall_s = time.perf_counter() - t0
         return out_idx, out_score, stats
 
+    # ------------------------------------------------------------------ embed
+    # Sentence embeddings [rows, H] instead of top-k, on the machinery of the classify forms:
+    # the stager, the two slots and their streams, one graph per slot for full batches, the
+    # power-of-two bucket graphs for small jobs, the full-batch step for a partial batch under
+    # batch invariance. The classify paths and their graphs are not touched.
+    @staticmethod
+    def _embed_key(pooling: str, normalize: bool) -> Tuple[str, bool]:
+        if pooling not in ("mean", "cls"):
+            raise ValueError("pooling must be 'mean' or 'cls'")
+        return str(pooling), bool(normalize)
+
+    def _embed_step(self, slot: int, rows: int, key: Tuple[str, bool]) -> torch.Tensor:
+        ids, lens = self.ids_s[slot], self.lens_s[slot]
+        self._tokenize(self.text[slot], self.offs[slot], ids=ids, lens=lens, rows=rows)
+        return self.model.embed(ids[:rows], lens[:rows], key[0], key[1])
+
+    def _warm(self, fn) -> None:
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):  # warm up allocator + code objects off-graph
+            fn()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+
+    def _embed_graph_step(self, slot: int, key: Tuple[str, bool]) -> torch.Tensor:
+        gk = (slot,) + key
+        if gk not in self._egraphs:
+            if not any(k[1:] == key for k in self._egraphs):  # the other slots' steps take the same kernels
+                self._warm(lambda: self._embed_step(slot, self.B, key))
+            # the slot's graphs replay in order on the slot's stream: one pool serves them all
+            if slot in self._graphs:
+                pool = self._graphs[slot][0].pool()
+            else:
+                pool = self._epools.setdefault(slot, torch.cuda.graph_pool_handle())
+            self._egraphs[gk] = capture_graph(lambda: self._embed_step(slot, self.B, key), pool=pool)
+        g, out = self._egraphs[gk]
+        g.replay()
+        return out
+
+    def _embed_slot(self, slot: int, rows: int, key: Tuple[str, bool]) -> torch.Tensor:
+        if rows < self.B and ops.batch_invariant():  # as run_slot: a partial batch runs the full-batch step
+            offs = self.offs[slot]
+            offs[rows + 1:].copy_(offs[rows:rows + 1].expand(self.B - rows))
+            rows = self.B
+        if self.use_graph and rows == self.B:
+            return self._embed_graph_step(slot, key)
+        return self._embed_step(slot, rows, key)
+
+    def _embed_bucket(self, bucket: int, key: Tuple[str, bool]) -> torch.Tensor:
+        def fn():
+            self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+            return self.model.embed(self.ids_s[0][:bucket], self.lens_s[0][:bucket], key[0], key[1])
+
+        if not self.use_graph:
+            return fn()
+        gk = ("embed", bucket) + key
+        if gk not in self._bgraphs:
+            self._warm(fn)
+            self._bgraphs[gk] = capture_graph(fn, pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def embed_texts(self, rows: Sequence, pooling: str = "mean", normalize: bool = True) -> EmbedResult:
+        """Embed an in-memory list of strings (small jobs; no CSV) -> host fp32 ``[n, H]``."""
+        key = self._embed_key(pooling, normalize)
+        out = []
+        for b0 in range(0, len(rows), self.B):
+            chunk = rows[b0:b0 + self.B]
+            text, offs = pack_rows(r[:self.max_row_bytes] if isinstance(r, (bytes, bytearray)) else
+                                   r.encode("utf-8")[:self.max_row_bytes] for r in chunk)
+            n = len(chunk)
+            if self.device.type == "cuda":
+                pin = self._pinned()
+                bk = self._bucket(n)
+                pin["text"][:text.size].copy_(torch.from_numpy(text))
+                pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
+                pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
+                if text.size:
+                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
+                self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
+                out.append(self._embed_bucket(bk, key)[:n].cpu())  # the D2H synchronizes: pinned rows free again
+            else:
+                ids, lens = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
+                out.append(self.model.embed(ids, lens, key[0], key[1]).float().cpu())
+        if not out:
+            return EmbedResult(0, torch.zeros((0, self.cfg.hidden), dtype=torch.float32))
+        return EmbedResult(len(rows), torch.cat(out))
+
+    def embed_table(self, table, start: int, n: int, col: int, pooling: str = "mean", normalize: bool = True,
+                    out: Optional[torch.Tensor] = None, stage_timing: bool = False,
+                    host_threads: Optional[int] = None) -> Tuple[torch.Tensor, RunStats]:
+        """Pipelined embedding of CSV rows ``[start, start+n)`` -> device fp32 ``emb[n, H]`` (left on
+        the GPU for a DP all-gather) and the run's stats; the pipeline of :meth:`classify_table`.
+        With ``stage_timing``, ``stats.timing_ms`` carries ``device_embed_ms`` (tokenize, encoder and
+        pooling, one graph), ``device_copy_out_ms`` and ``device_h2d_ms`` from hipEvent pairs."""
+        assert self.device.type == "cuda", "embed_table needs a ROCm device"
+        key = self._embed_key(pooling, normalize)
+        if host_threads is None:
+            from ..parallel.placement import host_threads as budget
+
+            host_threads = budget(8)
+        n = max(0, min(int(n), table.num_rows - int(start)))
+        dev = self.device
+        out = torch.empty((n, self.cfg.hidden), dtype=torch.float32, device=dev) if out is None else out
+        stats = RunStats()
+        if n == 0:
+            return out, stats
+        st = self._get_stager()
+        caller = torch.cuda.current_stream(dev)
+        streams = self.compute_streams or [caller] * self.n_slots
+        for s in streams:
+            if s is not caller:
+                s.wait_stream(caller)  # out and earlier work were enqueued on the caller's stream
+        cs = int(self.copy_stream.cuda_stream)
+        nb = (n + self.B - 1) // self.B
+        t0 = time.perf_counter()
+        tm = stats.timing_ms
+        dst = DeviceStages() if stage_timing else None
+        ev = DeviceStages.event
+
+        def stage(i: int) -> None:
+            if i < nb:
+                b1 = start + i * self.B
+                with span("host_csv_stage_ms", tm):
+                    st.submit(i % self.n_slots, table, b1, min(self.B, start + n - b1), col, self.max_row_bytes,
+                              host_threads)
+
+        stage(0)
+        for i in range(nb):
+            slot = i % self.n_slots
+            if self.n_slots > 1:  # batch i+1 stages into the other slot while batch i runs
+                stage(i + 1)
+            stream = streams[slot]
+            ks = int(stream.cuda_stream)
+            with torch.cuda.stream(stream):
+                with span("host_stager_wait_ms", tm):
+                    rows, _ = st.upload(slot, self.text[slot].data_ptr(), self.text[slot].numel(),
+                                        self.offs[slot].data_ptr(), cs, ks)
+                e0 = ev(stream) if dst else None
+                with span("host_launch_ms", tm):
+                    emb = self._embed_slot(slot, int(rows), key)
+                st.release(slot, ks)
+                if self.n_slots == 1:  # one slot: the next batch stages once this one released it
+                    stage(i + 1)
+                c0 = ev(stream) if dst else None
+                out[i * self.B:i * self.B + rows].copy_(emb[:rows], non_blocking=True)
+                if dst:
+                    dst.add("embed", e0, c0)
+                    dst.add("copy_out", c0, ev(stream))
+            stats.batches += 1
+        for s in streams:
+            if s is not caller:
+                caller.wait_stream(s)
+        with span("host_drain_ms", tm):
+            torch.cuda.synchronize(dev)
+        h2d_ms, _ = st.take_h2d_ms()
+        if dst:
+            dst.resolve(tm)
+            tm["device_h2d_ms"] = round(h2d_ms, 3)
+        stats.rows = n
+        stats.wall_s = time.perf_counter() - t0
+        return out, stats
+
     def memory_bytes(self) -> int:
         """Resident device bytes: weights, the LayerNorm-folded weight copies once built
         (they are ~45 % of the encoder weights), staging and token buffers."""
@@ -413,6 +586,10 @@ class ClassifyEngine:
         extra = sum(t.numel() * t.element_size() for t in folded.values())
         if self.vocab is not None and self.device.type == "cuda":
             extra += self.vocab.table_bytes  # the WordPiece table on this device
+        # embed: the static [rows, H] fp32 outputs its graphs hold (nothing until the first embed call)
+        egraphs = list(self._egraphs.values()) + [v for k, v in (getattr(self, "_bgraphs", None) or {}).items()
+                                                  if k[0] == "embed"]
+        extra += sum(o.numel() * o.element_size() for _, o in egraphs)
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

@@ -54,6 +54,7 @@ OP_TO_MODULE: Dict[str, str] = {
     # MI355X accelerator ops
     "map_classify": "map_classify",
     "map_classify_tpu": "map_classify",
+    "map_embed": "map_embed",
     "map_summarize": "map_summarize",
     # outbound side effects (opt-in only)
     "trigger_oracle": "trigger_oracle",

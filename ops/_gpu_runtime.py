@@ -16,6 +16,9 @@ optionally with query options ``bert-base?labels=5&seed=3&batch=512``, or a
 that json (relative to the model file; the query wins) gives the model a WordPiece
 vocabulary: its texts are then tokenized by ``atpu-wordpiece v1`` instead of the
 hash tokenizer.
+``"head": "none"`` in that json marks an encoder without pooler and classifier (a plain
+``BertModel`` export): the file need not hold ``pool_*`` / ``cls_*``, ``map_embed`` serves it
+and ``map_classify`` refuses it.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -48,6 +51,7 @@ class ModelSpec:
     quant: Optional[str] = None  # "?quant=int8": INT8 encoder GEMMs; None: the CLASSIFY_QUANT default
     vocab: Optional[str] = None  # vocab.txt of the model: the WordPiece tokenizer; None: the hash tokenizer
     lowercase: bool = True  # uncased vocabulary: ASCII A-Z folded before matching
+    head: bool = True  # False ("head": "none" in the json): an encoder without pooler / classifier (map_embed only)
 
 
 def _flag(value: Any) -> bool:
@@ -81,7 +85,8 @@ def parse_spec(path: str) -> ModelSpec:
         if lowercase is None:
             lowercase = _flag(meta.get("lowercase", True))
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
-                         file=base, quant=quant, vocab=vocab, lowercase=lowercase)
+                         file=base, quant=quant, vocab=vocab, lowercase=lowercase,
+                         head=str(meta.get("head", "classifier")).strip().lower() != "none")
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -108,10 +113,12 @@ def _load_host_pack(spec: ModelSpec, cfg):
 
         pack = ParamPack(param_specs(cfg))
         tensors = load_file(spec.file)
-        missing = [n for n in pack.names() if n not in tensors]
+        # "head": "none": the file need not hold the pooler / classifier; what it lacks stays zero
+        names = [n for n in pack.names() if spec.head or n in tensors or not n.startswith(("pool_", "cls_"))]
+        missing = [n for n in names if n not in tensors]
         if missing:
             raise KeyError(f"{spec.file}: missing tensors {missing[:4]}{' ...' if len(missing) > 4 else ''}")
-        for name in pack.names():
+        for name in names:
             pack[name].copy_(tensors[name])
         return pack
     return init_random(cfg, seed=spec.seed)
