@@ -231,6 +231,25 @@ PYBIND11_MODULE(_atpu, m) {
       "to the pooled vector when fin is given (0 = rows already normalised), optional L2 normalisation",
       py::arg("x"), py::arg("fin"), py::arg("gamma"), py::arg("beta"), py::arg("lens"), py::arg("out"), py::arg("B"),
       py::arg("S"), py::arg("H"), py::arg("mode"), py::arg("normalize"), py::arg("stream"));
+  m.def("sim_topk_splits", &sim_topk_splits, "the split count sim_topk_partial runs for a wanted one (no empty split)",
+        py::arg("N"), py::arg("want"));
+  m.def(
+      "sim_topk_partial",
+      [](uintptr_t q, uintptr_t c, uintptr_t ws, int nq, int N, int D, int k, int splits, uintptr_t stream) {
+        sim_topk_partial(P<const float>(q), P<const float>(c), P<float>(ws), nq, N, D, k, splits, S(stream));
+      },
+      "fp32 similarity GEMM with the top-k in the epilogue: every split's sorted top-k (value, row) to ws [nq, P, k, 2]",
+      py::arg("q"), py::arg("c"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("k"),
+      py::arg("P"), py::arg("stream"));
+  m.def(
+      "sim_topk_merge",
+      [](uintptr_t ws, uintptr_t scores, uintptr_t ids, int nq, int splits, int k, int kk, int64_t id_base,
+         uintptr_t stream) {
+        sim_topk_merge(P<const float>(ws), P<float>(scores), P<int64_t>(ids), nq, splits, k, kk, id_base, S(stream));
+      },
+      "merge of the per-split lists of sim_topk_partial in (value desc, row asc) order",
+      py::arg("ws"), py::arg("scores"), py::arg("ids"), py::arg("nq"), py::arg("P"), py::arg("k"), py::arg("kk"),
+      py::arg("id_base"), py::arg("stream"));
   m.def("decode_attention", [](uintptr_t q, int ldq, uintptr_t k, uintptr_t v, int ldkv, int seq_stride, int group,
                                uintptr_t lens, uintptr_t step_dev, uintptr_t hist, int hist_stride, uintptr_t bias,
                                int bias_stride, uintptr_t out, int ldo, int rows, int H, float scale, uintptr_t stream,

@@ -119,6 +119,19 @@ void cls_attend(const bf16* g, const float* fin, const bf16* U, const int32_t* l
 enum PoolMode : int { kPoolMean = 0, kPoolCls = 1 };
 void pool_embed(const bf16* x, const float* fin, const float* gamma, const float* beta, const int32_t* lens,
                 float* out, int B, int S, int H, int mode, int normalize, hipStream_t stream);
+// Top-k similarity search (sim_topk.hip): scores = q [nq, D] . c [N, D]^T in exact fp32 (one
+// k-ordered fmaf chain per pair, the order a function of D alone), the [nq, N] matrix never
+// written. sim_topk_partial leaves every split's sorted top-k (value, row as int bits) in
+// ws [nq, P, k, 2] fp32; sim_topk_merge reduces it to scores [nq, kk] / ids [nq, kk] =
+// id_base + row, ordered by (value desc, row asc). D % 64 == 0, D in [64, 1024], k in [1, 32],
+// kk = min(k, N), N < 2^31 - 256. P = sim_topk_splits(N, wanted) <= kSimMaxSplits (no empty split).
+// Nothing outside c[0:N] is read.
+constexpr int kSimMaxSplits = 256;
+int sim_topk_splits(int N, int want);
+void sim_topk_partial(const float* q, const float* c, float* ws, int nq, int N, int D, int k, int P,
+                      hipStream_t stream);
+void sim_topk_merge(const float* ws, float* scores, int64_t* ids, int nq, int P, int k, int kk, int64_t id_base,
+                    hipStream_t stream);
 
 // ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
 // Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),

@@ -17,6 +17,7 @@ from .attention import attention_packed, attention  # noqa: F401
 from .qkv_attention import qkv_attention, qkv_attention_ok, qkv_head_order  # noqa: F401
 from .cls_attend import cls_attend, cls_attend_ok, cls_attend_ref, cls_reassoc_weights  # noqa: F401
 from .pool import pool_embed, pool_embed_ok, pool_embed_ref  # noqa: F401
+from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .head import classify_head_topk  # noqa: F401

@@ -13,8 +13,10 @@ fault, which drops that rank from the DP group (elastic shrink, SURVEY.md
 §5.3) while the job that hit it fails and names the rank.
 
 Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
-``risk_accumulate`` (C3 all-reduce of {count,sum,min,max}) and
-``map_summarize`` (C5 all-gather of generated token ids).
+``risk_accumulate`` (C3 all-reduce of {count,sum,min,max}),
+``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
+tasks (C2 all-gather of embeddings) and ``map_search`` (C2 all-gather of
+per-rank top-k lists, merged on rank 0).
 """
 from __future__ import annotations
 
@@ -535,6 +537,28 @@ def embed_batch_task(payload: Dict[str, Any]) -> Any:
     payloads = payload["payloads"]
     h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
     return me.embed_batch(h, payloads, rank, ws)
+
+
+# --------------------------------------------------------------- map_search
+@dp_task("map_search")
+def search_task(payload: Dict[str, Any]) -> Any:
+    """One map_search job: every rank embeds the queries and searches its ``split_range`` slice of the
+    corpus with ``id_base`` = the slice start; the per-rank top-k lists are all-gathered (C2) and
+    merged on rank 0 in the kernel's total order (:func:`ops.map_search.search_queries`)."""
+    from ops import map_search as ms
+
+    rank, ws = world()
+    return ms.search_one(payload, rank, ws)
+
+
+@dp_task("map_search_batch")
+def search_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several ``queries`` + ``corpus_uri`` jobs of one lease (same model, pooling, metric and corpus):
+    :func:`ops.map_search.search_batch` on every rank."""
+    from ops import map_search as ms
+
+    rank, ws = world()
+    return ms.search_batch(payload["payloads"], rank, ws)
 
 
 # ---------------------------------------------------------- risk_accumulate

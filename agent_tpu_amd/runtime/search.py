@@ -1,0 +1,148 @@
+"""Device-resident corpora for ``map_search`` and the search over them.
+
+A corpus is a 2-D C-order ``.npy`` of ``float32`` or ``float16`` rows: exactly what ``map_embed``
+writes with ``output: "npy"``. :func:`load_corpus` memory-maps it, so a DP rank touches only its
+``[start, start + count)`` slice, widens ``float16`` to fp32 once, normalises the rows on the
+device for the cosine metric (one-time work per index, not the hot path), refuses non-finite
+values, and keeps the loaded slices in a small LRU keyed by the file's identity (a rewritten file
+misses). :func:`search` is ``ops.sim_topk`` on the GPU and its PyTorch twin on a CPU engine.
+"""
+from __future__ import annotations
+
+import os
+import threading
+from collections import OrderedDict
+from typing import Any, Dict, NamedTuple, Tuple
+
+import torch
+
+EPS = 1e-12  # F.normalize's, as pool_embed
+
+#: the loader's input errors (``ops/map_search.py`` lists them in its own ``ERRORS``)
+ERRORS: Dict[str, str] = {
+    "corpus_file": "corpus_uri must be a local 2-D float32 or float16 .npy file",
+    "corpus_empty": "corpus has no rows",
+    "corpus_nonfinite": "corpus holds non-finite values",
+    "corpus_too_large": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float32",
+}
+
+
+class Corpus(NamedTuple):
+    vectors: torch.Tensor  # [count, dim] fp32 on the device, contiguous
+    start: int  # row of the file that vectors[0] is
+    total: int  # rows of the whole file
+    cached: bool  # served from the LRU
+
+
+_lock = threading.Lock()
+_cache: "OrderedDict[Tuple, torch.Tensor]" = OrderedDict()
+
+
+def lru_capacity() -> int:
+    return max(1, int(os.getenv("SEARCH_INDEX_LRU_SIZE", "2")))
+
+
+def max_bytes() -> int:
+    return int(float(os.getenv("SEARCH_INDEX_MAX_GB", "64")) * 2 ** 30)
+
+
+def local_path(uri: Any) -> str:
+    if not isinstance(uri, str) or not uri or ("://" in uri and not uri.startswith("file://")):
+        raise ValueError(ERRORS["corpus_file"])
+    return uri[len("file://"):] if uri.startswith("file://") else uri
+
+
+def open_corpus(uri: Any):
+    """-> (memory-mapped array, realpath, stat); the file's shape and dtype checked, nothing read."""
+    import numpy as np
+
+    path = os.path.realpath(local_path(uri))
+    try:
+        st = os.stat(path)
+        arr = np.load(path, mmap_mode="r", allow_pickle=False)
+    except (OSError, ValueError, EOFError):
+        raise ValueError(ERRORS["corpus_file"]) from None
+    if not isinstance(arr, np.ndarray) or arr.ndim != 2 or arr.dtype.str not in ("<f4", "<f2") \
+            or not arr.flags["C_CONTIGUOUS"]:
+        raise ValueError(ERRORS["corpus_file"])
+    if arr.shape[0] == 0 or arr.shape[1] == 0:
+        raise ValueError(ERRORS["corpus_empty"])
+    return arr, path, st
+
+
+def corpus_shape(uri: Any) -> Tuple[int, int]:
+    arr, _, _ = open_corpus(uri)
+    return int(arr.shape[0]), int(arr.shape[1])
+
+
+def normalize_rows(x: torch.Tensor) -> torch.Tensor:
+    return x / x.norm(dim=1, keepdim=True).clamp_min(EPS)
+
+
+def load_corpus(uri: Any, start: int = 0, count: int = -1, normalize: bool = True,
+                device: torch.device = torch.device("cpu")) -> Corpus:
+    """Rows ``[start, start + count)`` (``count < 0``: to the end) of the file as fp32 on ``device``."""
+    import numpy as np
+
+    arr, path, st = open_corpus(uri)
+    total, dim = int(arr.shape[0]), int(arr.shape[1])
+    start = max(0, min(int(start), total))
+    count = total - start if count < 0 else max(0, min(int(count), total - start))
+    key = (path, st.st_mtime_ns, st.st_size, start, count, bool(normalize), str(device))
+    with _lock:
+        hit = _cache.get(key)
+        if hit is not None:
+            _cache.move_to_end(key)
+            return Corpus(hit, start, total, True)
+    if count * dim * 4 > max_bytes():  # before any allocation
+        raise ValueError(ERRORS["corpus_too_large"])
+    host = torch.from_numpy(np.array(arr[start:start + count], order="C"))  # a copy: only this slice is read
+    vec = host.to(device).to(torch.float32)  # float16 is widened once, here
+    if not bool(torch.isfinite(vec).all()):
+        raise ValueError(ERRORS["corpus_nonfinite"])
+    if normalize:
+        vec = normalize_rows(vec)
+    vec = vec.contiguous()
+    with _lock:
+        _cache[key] = vec
+        _cache.move_to_end(key)
+        while len(_cache) > lru_capacity():
+            _cache.popitem(last=False)
+    return Corpus(vec, start, total, False)
+
+
+def clear_cache() -> None:
+    with _lock:
+        _cache.clear()
+
+
+def cache_info() -> Dict[str, Any]:
+    with _lock:
+        return {"entries": [k[0] for k in _cache], "capacity": lru_capacity(),
+                "resident_bytes": sum(v.numel() * 4 for v in _cache.values())}
+
+
+def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0
+           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scores ``[nq, kk]`` fp32, ids ``[nq, kk]`` int64) of the fp32 ``qvecs [nq, dim]`` against
+    ``corpus [rows, dim]`` on the corpus's device, ordered by (score desc, id asc). An empty slice
+    (a DP rank beyond the corpus) gives ``kk = 0``. A shape the kernel does not take is an error,
+    never a detour through PyTorch."""
+    from .. import ops
+
+    q = qvecs.to(device=corpus.device, dtype=torch.float32).contiguous()
+    if corpus.shape[0] == 0:
+        return (torch.empty((q.shape[0], 0), dtype=torch.float32, device=corpus.device),
+                torch.empty((q.shape[0], 0), dtype=torch.int64, device=corpus.device))
+    if not corpus.is_cuda:
+        return ops.sim_topk_ref(q, corpus, k, id_base)
+    return ops.sim_topk(q, corpus, k, id_base)
+
+
+def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The best ``k`` columns of every row of ``scores`` / ``ids [nq, m]`` in the (score desc, id asc)
+    order: two stable sorts, the minor key first. Padding is ``(-inf, 2^62)`` and sorts last."""
+    by_id = torch.sort(ids, dim=1, stable=True).indices
+    s1, i1 = torch.gather(scores, 1, by_id), torch.gather(ids, 1, by_id)
+    by_score = torch.sort(s1 + 0.0, dim=1, descending=True, stable=True).indices[:, :k]
+    return torch.gather(s1, 1, by_score), torch.gather(i1, 1, by_score)

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Isolated ``sim_topk`` against ``torch.topk(q @ c.T, k)`` on one MI355X.
+
+A: ``ops.sim_topk(q, c, k)``: the fp32 similarity GEMM with the top-k in its epilogue (the
+``[queries, N]`` scores never written). B: the same tensors through torch: an fp32 GEMM that
+writes the scores, then ``torch.topk``. D = 768, ``top_k`` 10, N in ``--rows`` and the query counts
+in ``--queries``. A corpus smaller than 512 MiB rotates through ``--buffers`` copies so that no call
+finds it in the 256 MiB Infinity Cache. A and B alternate for ``--rounds`` rounds in one process;
+one JSON line per (N, queries, variant, round): us per call from hipEvents after warm-up, the
+effective corpus rate ``N * D * 4 / t`` in TB/s (for B too: what the same answer costs per corpus
+byte), and TF/s (``2 * queries * N * D / t``). ``--splits`` overrides the automatic split count.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
+    ap.add_argument("--queries", type=int, nargs="+", default=[1, 32, 256])
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--top-k", type=int, default=10)
+    ap.add_argument("--splits", type=int, default=0)
+    ap.add_argument("--buffers", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
+        return 3
+    from agent_tpu_amd import ops
+
+    dev = torch.device("cuda", 0)
+    D, k = a.dim, a.top_k
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N in a.rows:
+        nbuf = a.buffers if N * D * 4 < 512 * 2 ** 20 else 1
+        cs = [torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=gen), dim=1) for _ in range(nbuf)]
+        for nq in a.queries:
+            q = torch.nn.functional.normalize(torch.randn(nq, D, device=dev, generator=gen), dim=1)
+
+            def fused(i):
+                return ops.sim_topk(q, cs[i], k, splits=a.splits or None)
+
+            def partner(i):
+                return torch.topk(q @ cs[i].T, k)
+
+            def timed(fn):
+                for i in range(max(nbuf, 2)):
+                    fn(i % nbuf)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for it in range(a.iters):
+                    fn(it % nbuf)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
+
+            same = torch.equal(fused(0)[1], partner(0)[1])  # random data: no ties expected
+            for r in range(a.rounds):
+                for variant, fn in (("sim_topk", fused), ("torch_matmul_topk", partner)):
+                    us = timed(fn)
+                    print(json.dumps({"bench": "search", "variant": variant, "N": N, "queries": nq, "dim": D, "top_k": k,
+                                      "round": r, "us_per_call": round(us, 2),
+                                      "corpus_tbs": round(N * D * 4 / us / 1e6, 3),
+                                      "tflops": round(2.0 * nq * N * D / us / 1e6, 2),
+                                      "ids_equal_between_variants": same}), flush=True)
+        del cs
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
