@@ -92,18 +92,18 @@ PYBIND11_MODULE(_atpu, m) {
       "gemm_ln",
       [](uintptr_t A, int lda, uintptr_t Bt, int ldb, uintptr_t C, int ldc, uintptr_t bias, uintptr_t R, int ldr, int M,
          int N, int K, int epi, uintptr_t in_fin, uintptr_t colsum, uintptr_t res_fin, uintptr_t gamma,
-         uintptr_t part_out, uintptr_t stream) {
+         uintptr_t part_out, uintptr_t stream, int layout) {
         GemmArgs g;
         g.A = P<const bf16>(A); g.lda = lda; g.Bt = P<const bf16>(Bt); g.ldb = ldb; g.C = P<bf16>(C); g.ldc = ldc;
         g.bias = P<const float>(bias); g.R = P<const bf16>(R); g.ldr = ldr; g.M = M; g.N = N; g.K = K; g.epi = epi;
         g.in_fin = P<const float>(in_fin); g.colsum = P<const float>(colsum); g.res_fin = P<const float>(res_fin);
-        g.gamma = P<const float>(gamma); g.part_out = P<float>(part_out);
+        g.gamma = P<const float>(gamma); g.part_out = P<float>(part_out); g.layout = layout;
         gemm_bf16(g, S(stream));
       },
       "bf16 MFMA GEMM with LayerNorm folding epilogues (InNorm / ResNorm / StatsOut)", py::arg("A"), py::arg("lda"),
       py::arg("Bt"), py::arg("ldb"), py::arg("C"), py::arg("ldc"), py::arg("bias"), py::arg("R"), py::arg("ldr"),
       py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("in_fin"), py::arg("colsum"),
-      py::arg("res_fin"), py::arg("gamma"), py::arg("part_out"), py::arg("stream"));
+      py::arg("res_fin"), py::arg("gamma"), py::arg("part_out"), py::arg("stream"), py::arg("layout") = 0);
   m.def(
       "gemm_i8",
       [](uintptr_t A, int lda, uintptr_t a_scale, uintptr_t Bt, int ldb, uintptr_t b_scale, uintptr_t C, int ldc,
@@ -147,17 +147,17 @@ PYBIND11_MODULE(_atpu, m) {
   m.def(
       "qkv_attention",
       [](uintptr_t A, int lda, uintptr_t Bt, int ldb, uintptr_t ctx, int ldo, uintptr_t bias, int M, int N, int K,
-         int epi, uintptr_t in_fin, uintptr_t colsum, uintptr_t lens, float scale, uintptr_t stream) {
+         int epi, uintptr_t in_fin, uintptr_t colsum, uintptr_t lens, float scale, uintptr_t stream, int layout) {
         GemmArgs g;
         g.A = P<const bf16>(A); g.lda = lda; g.Bt = P<const bf16>(Bt); g.ldb = ldb; g.C = P<bf16>(ctx); g.ldc = ldo;
         g.bias = P<const float>(bias); g.M = M; g.N = N; g.K = K; g.epi = epi;
-        g.in_fin = P<const float>(in_fin); g.colsum = P<const float>(colsum);
+        g.in_fin = P<const float>(in_fin); g.colsum = P<const float>(colsum); g.layout = layout;
         qkv_attention(g, P<const int32_t>(lens), scale, S(stream));
       },
       "BERT QKV projection + self-attention (S = 128) in one persistent kernel; Bt rows per head [Q|K|V]",
       py::arg("A"), py::arg("lda"), py::arg("Bt"), py::arg("ldb"), py::arg("ctx"), py::arg("ldo"), py::arg("bias"),
       py::arg("M"), py::arg("N"), py::arg("K"), py::arg("epi"), py::arg("in_fin"), py::arg("colsum"),
-      py::arg("lens"), py::arg("scale"), py::arg("stream"));
+      py::arg("lens"), py::arg("scale"), py::arg("stream"), py::arg("layout") = 0);
   m.def(
       "ln_stats_finalize",
       [](uintptr_t part, int slots, int M, int K, float eps, uintptr_t fin, uintptr_t stream) {

@@ -50,6 +50,9 @@ enum GemmEpilogue : int {
                         //   values of each row's 32-column slabs
 };
 
+// GemmArgs::layout bits
+constexpr int kLayA = 1, kLayC = 2, kLayR = 4;
+
 struct GemmArgs {
   const bf16* A = nullptr;  // [M, K] row-major, leading dim lda
   int lda = 0;
@@ -62,6 +65,13 @@ struct GemmArgs {
   int ldr = 0;
   int M = 0, N = 0, K = 0;
   int epi = 0;
+  // operand layout (kLayA | kLayC | kLayR): the operand [M, W] lies in K-tile image order
+  // [M/256][W/64][256][64] (element (r, c) at (((r/256)*(W/64) + c/64)*256 + r%256)*64 + c%64)
+  // with W = its leading dimension; one image is a K-tile of the consuming 256x256 GEMM's A
+  // operand and the 64 columns one wave of the producing GEMM writes. 0 = row-major.
+  // Persistent full-line 256x256 kernel (M, N % 256 == 0) and the fused QKV + attention
+  // kernel (A, and C = the context: head h of a 2-sequence tile is image h of its row tile).
+  int layout = 0;
   // split-K (skinny M): splits > 1 needs ws = fp32 [splits, M, N]
   int splits = 1;
   float* ws = nullptr;

@@ -746,10 +746,19 @@ struct LnLds {
   float* st = nullptr;
 };
 
+// first row (in 64-element rows) of wave (wm, wn)'s 128 x 64 block of tile (m0, n0) in an
+// image-order [M, W] tensor
+__device__ __forceinline__ size_t img_row0(int m0, int n0, int wm, int wn, int W) {
+  return ((size_t)(m0 >> 8) * (W >> 6) + (n0 >> 6) + wn) * 256 + wm * 128;
+}
+
 // IN_ACC (InNorm): the caller started the accumulators at -mu*colsum (else the
 // epilogue applies -rstd*mu*colsum itself, from LDS colsum)
 // NOST (timing-only ablation, results WRONG): the output values are computed but not stored
-template <int EPI, bool NT, bool IN_ACC = true, int GM = 0, bool NOST = false>
+// LAY (kLayC / kLayR bits): C / R in K-tile image order [M/256][W/64][256][64] (W = ldc / ldr):
+// the wave's 128 x 64 block is rows wm*128.. of image (m0/256, n0/64 + wn), 128-B rows, so
+// every store / residual load instruction covers 1 KiB contiguous; same instruction count
+template <int EPI, bool NT, bool IN_ACC = true, int GM = 0, bool NOST = false, int LAY = 0>
 __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int m0, int n0, int wm, int wn, int lane,
                                                   bf16* __restrict__ C, int ldc, const bf16* __restrict__ R, int ldr,
                                                   const float* lds_bias, char* scratch,
@@ -783,6 +792,12 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
   auto frag_off = [&](int j) { return fr * 128 + (((j * 2 + (fc >> 1)) ^ (fr & 7)) << 4) + (fc & 1) * 8; };
   const size_t row0 = (size_t)(m0 + wm * 128);
   const int col = n0 + wn * 64 + lc * 8;
+  constexpr bool kCImg = LAY & kLayC, kRImg = LAY & kLayR;
+  // image order = a row-major [*, 64] array whose row 0 is the image's first row
+  const size_t crow0 = kCImg ? img_row0(m0, n0, wm, wn, ldc) : row0;
+  const size_t rrow0 = kRImg ? img_row0(m0, n0, wm, wn, ldr) : row0;
+  const int cld = kCImg ? 64 : ldc, ccol = kCImg ? lc * 8 : col;
+  const int rld = kRImg ? 64 : ldr, rcol = kRImg ? lc * 8 : col;
   // all 16 residual loads go out at once (64 VGPRs: the operand fragments are
   // dead here). Loading one 16-row block ahead left every other block waiting
   // a full memory latency (~4 latencies per tile: o-proj ran 38 % over its main
@@ -797,9 +812,9 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
     }
 #pragma unroll
     for (int i = 2; i < 8; ++i) {
-      const bf16* rp = R + (row0 + i * 16 + lr) * ldr + col;
+      const bf16* rp = R + (rrow0 + i * 16 + lr) * rld + rcol;
       res[i][0] = load16_untracked(rp);
-      res[i][1] = load16_untracked(rp + 8 * (size_t)ldr);
+      res[i][1] = load16_untracked(rp + 8 * (size_t)rld);
     }
   }
 #pragma unroll
@@ -895,8 +910,8 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
     }
     const u32x4 o0 = *reinterpret_cast<const u32x4*>(scratch + line_off0);
     const u32x4 o1 = *reinterpret_cast<const u32x4*>(scratch + line_off1);
-    u32x4* cp = reinterpret_cast<u32x4*>(C + (row0 + i * 16 + lr) * ldc + col);
-    u32x4* cp1 = reinterpret_cast<u32x4*>(C + (row0 + i * 16 + lr + 8) * ldc + col);
+    u32x4* cp = reinterpret_cast<u32x4*>(C + (crow0 + i * 16 + lr) * cld + ccol);
+    u32x4* cp1 = reinterpret_cast<u32x4*>(C + (crow0 + i * 16 + lr + 8) * cld + ccol);
     if constexpr (NOST) {
       asm volatile("" ::"v"(o0), "v"(o1), "v"(cp), "v"(cp1));
     } else if constexpr (NT) {
@@ -949,7 +964,7 @@ struct LnFold {
 //    NEXT tile (or a barrier after the loop, for the last tile) sums the 4 column
 //    slots in order and stores the tile's 256 (sum, sumsq) pairs. The statistics are
 //    finalized between the kernels (ln_stats_finalize, norm_embed.hip).
-template <int EPI, int DBG = 0, bool NT = false, bool LINE = false>
+template <int EPI, int DBG = 0, bool NT = false, bool LINE = false, int LAY = 0>
 __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
     const bf16* __restrict__ A, int lda, const bf16* __restrict__ Bt, int ldb, bf16* __restrict__ C, int ldc,
     const float* __restrict__ bias, const bf16* __restrict__ R, int ldr, int M, int N, int K, LnFold lf) {
@@ -964,6 +979,10 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
   constexpr int kEpiOff = kBiasOff + 2 * 256 * 4;  // LINE epilogue: 2 KiB scratch per wave
   constexpr bool kIn = EPI & kEpiInNorm, kRes = EPI & kEpiResNorm, kSt = EPI & kEpiStatsOut;
   static_assert(!(kIn || kRes || kSt) || LINE, "LayerNorm folding needs the full-line epilogue");
+  static_assert(!LAY || LINE, "image-order operands need the full-line epilogue");
+  // A in K-tile image order (lda = K): K-tile kt of row tile tm0 is the contiguous 32 KB image
+  // (tm0/256)*(K/64) + kt, its rows 128 B apart: a DMA piece (8 rows) is 1 KiB contiguous
+  constexpr bool kAImg = LAY & kLayA;
   static_assert(!(kIn && (kRes || kSt)), "InNorm and ResNorm/StatsOut do not share one kernel (LDS budget)");
   constexpr int kXOff = kEpiOff + (LINE ? 8 * 2048 : 0);
   constexpr int kFinOff = kXOff;                                    // [2 tiles (InNorm)][256][2] (rstd, rstd*mu)
@@ -1031,15 +1050,17 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int r = qrow(q, (i * 8 + wave) * 8 + (ln >> 3));
-        const size_t e = (q == 0 || q == 3) ? (size_t)min(tm0 + r, M - 1) * lda + sw(r, ln & 7) * 8
-                                            : (size_t)(tn0 + r) * ldb + sw(r, ln & 7) * 8;
+        const size_t e = (q == 0 || q == 3)
+                             ? (kAImg ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + sw(r, ln & 7) * 8
+                                      : (size_t)min(tm0 + r, M - 1) * lda + sw(r, ln & 7) * 8)
+                             : (size_t)(tn0 + r) * ldb + sw(r, ln & 7) * 8;
         if constexpr (kFold) soff[q][i] = (uint32_t)(e * 2);
         else src[q][i] = ((q == 0 || q == 3) ? A : Bt) + e;
       }
   };
   auto stage = [&](int q, int kt, int buf) {
     char* base = lds + buf * 2 * kImg;
-    const int koff = kt * 64;
+    const int koff = (kAImg && (q == 0 || q == 3)) ? kt * (256 * 64) : kt * 64;
     if constexpr (kFold) {
       const char* g = reinterpret_cast<const char*>((q == 0 || q == 3) ? A : Bt) + koff * 2;
       glds16(g + soff[q][0], base + dst[q][0]);
@@ -1270,15 +1291,18 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
           // the lane id, opaque so it is not hoisted and kept live), row steps
           // as scalar offsets - the 64-bit address math spilled
           const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-              const_cast<bf16*>(R + (size_t)(cm0 + wm * 128) * ldr + cn0 + wn * 64), 0, 0x7fffffff, 0x00020000);
+              const_cast<bf16*>((LAY & kLayR) ? R + img_row0(cm0, cn0, wm, wn, ldr) * 64
+                                              : R + (size_t)(cm0 + wm * 128) * ldr + cn0 + wn * 64),
+              0, 0x7fffffff, 0x00020000);
+          const int rld = (LAY & kLayR) ? 64 : ldr;
           int l2 = __lane_id();
           asm volatile("" : "+v"(l2));
-          const int vo = ((l2 >> 3) * ldr + (l2 & 7) * 8) * 2;
+          const int vo = ((l2 >> 3) * rld + (l2 & 7) * 8) * 2;
 #pragma unroll
           for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              const int so = (i * 16 + h * 8) * ldr * 2;
+              const int so = (i * 16 + h * 8) * rld * 2;
               // untracked (see load16_untracked); the epilogue waits for it
               asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(pre[i][h]) : "v"(vo), "s"(rs), "s"(so) : "memory");
             }
@@ -1318,7 +1342,7 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
       constexpr int kEpiRun0 = kBiasAcc ? (EPI & ~kEpiBias) : EPI;
       constexpr int kEpiRun = (DBG & 8) ? (kEpiRun0 & ~(kEpiInNorm | kEpiResNorm | kEpiStatsOut)) : kEpiRun0;
       if constexpr (LINE)
-        epilogue_256_line<kEpiRun, NT, kInAcc, ((DBG >> 5) & 3), bool(DBG & 256)>(
+        epilogue_256_line<kEpiRun, NT, kInAcc, ((DBG >> 5) & 3), bool(DBG & 256), LAY>(
             acc, cm0, cn0, wm, wn, (kIn || kRes || kSt) ? opaque_lane() : lane, C, ldc, R, ldr,
             reinterpret_cast<const float*>(lds + kBiasOff) + tile_par * 256, lds + kEpiOff + wave * 2048, pre,
             LnLds{reinterpret_cast<const float*>(lds + kFinOff + (kInAcc ? tile_par * 2048 : 0)),
@@ -1395,6 +1419,31 @@ void launch_256s(const GemmArgs& g, hipStream_t s) {
     hipLaunchKernelGGL((gemm256s_kernel<E, 0, NT, LINE>), dim3(nb), dim3(512), 0, s, g.A, g.lda, g.Bt, g.ldb, g.C, g.ldc, \
                        g.bias, g.R, g.ldr, g.M, g.N, g.K, lf);                                                 \
     break;
+  if constexpr (LINE && NT) {
+    if (g.layout) {
+      // K-tile image order operands (GemmArgs::layout): the combinations the folded BERT
+      // encoder runs, and plain bias
+#define ATPU_G256S_LAY(E, L)                                                                                       \
+  if (g.epi == (E) && g.layout == (L)) {                                                                           \
+    hipLaunchKernelGGL((gemm256s_kernel<E, 0, NT, LINE, L>), dim3(nb), dim3(512), 0, s, g.A, g.lda, g.Bt, g.ldb, g.C, \
+                       g.ldc, g.bias, g.R, g.ldr, g.M, g.N, g.K, lf);                                              \
+    return;                                                                                                        \
+  }
+      ATPU_G256S_LAY(kEpiBias | kEpiInNorm | kEpiGelu, kLayC)
+      ATPU_G256S_LAY(kEpiBias | kEpiInNorm | kEpiGelu, kLayA | kLayC)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kLayA)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kLayA | kLayR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kLayA | kLayC | kLayR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiStatsOut, kLayA)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiStatsOut, kLayA | kLayC)
+      ATPU_G256S_LAY(kEpiBias, kLayA)
+      ATPU_G256S_LAY(kEpiBias, kLayC)
+      ATPU_G256S_LAY(kEpiBias, kLayA | kLayC)
+#undef ATPU_G256S_LAY
+      throw std::invalid_argument("atpu: no image-order GEMM for epilogue " + std::to_string(g.epi) + " layout " +
+                                  std::to_string(g.layout));
+    }
+  }
   if constexpr (LINE) {
     switch (g.epi) {
       ATPU_G256S(kEpiBias | kEpiInNorm)
@@ -2594,6 +2643,17 @@ void gemm_bf16(const GemmArgs& g, hipStream_t stream) {
   // times over; the 128x128 kernel (2 blocks/CU) covers small M and odd N.
   // ATPU_GEMM_TILE=128|256 forces one (benchmarks/tests).
   const int forced = gemm_force_tile(-1);
+  if (g.layout) {
+    // K-tile image order [M/256][W/64][256][64] of A / C / R: the persistent full-line kernel
+    // with nt stores only; the leading dimension of such an operand is its width W
+    ATPU_CHECK(!(g.layout & ~(kLayA | kLayC | kLayR)) && gemm_256_variant(-1) == 4 && !forced && g.splits <= 1,
+               "gemm: image-order operands need the default 256x256 kernel, no split-K");
+    ATPU_CHECK(g.M % 256 == 0 && g.N % 256 == 0, "gemm: image-order operands need M, N % 256 == 0");
+    ATPU_CHECK(!(g.layout & kLayA) || g.lda == g.K, "gemm: image-order A needs lda == K");
+    ATPU_CHECK(!(g.layout & kLayC) || g.ldc == g.N, "gemm: image-order C needs ldc == N");
+    ATPU_CHECK(!(g.layout & kLayR) || ((g.epi & kEpiResidual) && g.ldr == g.N),
+               "gemm: image-order R needs a residual, ldr == N");
+  }
   if (few_exact_ok(g) && !(g.epi & kEpiRowLn && !(g.epi & kEpiRowStats) && g.part_out)) {
     // batch-invariant mode, <= 16 rows: the dec kernel's exact arithmetic without its LDS ring
     if (g.epi & kEpiKvScatter)
@@ -2685,6 +2745,12 @@ void gemm_bf16(const GemmArgs& g, hipStream_t stream) {
       launch_dec(g, stream);
     else
       launch_tile<128, 128, 2, 2>(g, stream);
+    ATPU_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (g.layout) {
+    ATPU_CHECK(big_ok, "gemm: image-order operands need 16-byte aligned C / R");
+    launch_256s<true, true>(g, stream);
     ATPU_HIP_CHECK(hipGetLastError());
     return;
   }

@@ -47,7 +47,11 @@ constexpr int hq_rounds(int q) { return q == 2 ? 1 : 2; }
 
 constexpr int kAImg = kAttnImg;  // attention images (MODE 2): lds_ops.h
 
-template <int EPI, int MODE>
+// LAY (MODE 2; kLayA / kLayC, GemmArgs::layout): A and / or the context in K-tile image order
+// [M/256][W/64][256][64] (W = lda = K / ldc). A K-tile is one contiguous 32 KB image, a DMA
+// piece 1 KiB contiguous; head h of the tile is image h of the context's row tile, each wave's
+// 32 rows 4 KiB contiguous. LDS images, op counts and waits are unchanged.
+template <int EPI, int MODE, int LAY = 0>
 __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict__ A, int lda,
                                                           const bf16* __restrict__ Bt, int ldb,
                                                           bf16* __restrict__ C, int ldc,
@@ -96,14 +100,17 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict
 #pragma unroll
       for (int i = 0; i < hq_rounds(q); ++i) {
         const int r = hq_row(q, (i * 8 + wave) * 8 + (ln >> 3));
-        const size_t e = (q == 0 || q == 3) ? (size_t)(tm0 + r) * lda + hsw(r, ln & 7) * 8
-                                            : (size_t)(tn0 + r) * ldb + hsw(r, ln & 7) * 8;
+        const size_t e = (q == 0 || q == 3)
+                             ? ((LAY & kLayA) ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + hsw(r, ln & 7) * 8
+                                              : (size_t)(tm0 + r) * lda + hsw(r, ln & 7) * 8)
+                             : (size_t)(tn0 + r) * ldb + hsw(r, ln & 7) * 8;
         soff[q][i] = (uint32_t)(e * 2);
       }
   };
   auto stage = [&](int q, int kt, int buf) {
     char* base = lds + buf * kHBuf;
-    const char* g = reinterpret_cast<const char*>((q == 0 || q == 3) ? A : Bt) + kt * 128;
+    const char* g = reinterpret_cast<const char*>((q == 0 || q == 3) ? A : Bt) +
+                    (((LAY & kLayA) && (q == 0 || q == 3)) ? kt * (256 * 128) : kt * 128);
 #pragma unroll
     for (int i = 0; i < hq_rounds(q); ++i) glds16(g + soff[q][i], base + dst[q][i]);
   };
@@ -358,12 +365,15 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict
     }
     const int l2 = opaque_lane();
     const int lr = l2 >> 3, lc8 = l2 & 7;
-    bf16* obase = C + (size_t)(tm0 + wm * 128 + wn * 32 + lr) * ldc + h * 64 + lc8 * 8;
+    constexpr bool kCImg = LAY & kLayC;
+    const int old = kCImg ? 64 : ldc;
+    bf16* obase = kCImg ? C + ((((size_t)(tm0 >> 8) * (ldc >> 6) + h) * 256 + wm * 128 + wn * 32 + lr) * 64 + lc8 * 8)
+                        : C + (size_t)(tm0 + wm * 128 + wn * 32 + lr) * ldc + h * 64 + lc8 * 8;
 #pragma unroll
     for (int hh = 0; hh < 4; ++hh) {
       const int ro = hh * 8 + lr;
       const u32x4 val = *reinterpret_cast<const u32x4*>(ost + ro * 128 + asw(ro, lc8) * 16);
-      u32x4* dst = reinterpret_cast<u32x4*>(obase + (size_t)(hh * 8) * ldc);
+      u32x4* dst = reinterpret_cast<u32x4*>(obase + (size_t)(hh * 8) * old);
       *dst = val;
     }
   };
@@ -595,6 +605,23 @@ static void launch_256h(const GemmArgs& g, int mode, const int32_t* lens, float 
   const int tiles = (g.M / 256) * (g.N / 192);
   int nb = std::min(tiles, num_cus());
   if (nb >= 8) nb &= ~7;
+  if (g.layout) {
+    ATPU_CHECK(mode == 2 && !(g.layout & ~(kLayA | kLayC)), "qkv_attention: image order for A and the context only");
+    ATPU_CHECK(!(g.layout & kLayA) || g.lda == g.K, "qkv_attention: image-order A needs lda == K");
+    ATPU_CHECK(!(g.layout & kLayC) || g.ldc == g.N / 3, "qkv_attention: image-order context needs ldo == N / 3");
+#define ATPU_GHL(E, L)                                                                                          \
+  if (g.epi == (E) && g.layout == (L)) {                                                                        \
+    hipLaunchKernelGGL((gemm256h_kernel<E, 2, L>), dim3(nb), dim3(512), 0, s, g.A, g.lda, g.Bt, g.ldb, g.C, g.ldc, \
+                       g.bias, g.in_fin, g.colsum, g.M, g.N, g.K, lens, scale);                                 \
+    ATPU_HIP_CHECK(hipGetLastError());                                                                          \
+    return;                                                                                                     \
+  }
+    ATPU_GHL(kEpiBias, kLayC)
+    ATPU_GHL(kEpiBias | kEpiInNorm, kLayC)
+    ATPU_GHL(kEpiBias | kEpiInNorm, kLayA | kLayC)
+#undef ATPU_GHL
+    ATPU_CHECK(false, "qkv_attention: no image-order kernel for this epilogue / layout");
+  }
 #define ATPU_GH(E, MD)                                                                                          \
   hipLaunchKernelGGL((gemm256h_kernel<E, MD>), dim3(nb), dim3(512), 0, s, g.A, g.lda, g.Bt, g.ldb, g.C, g.ldc, \
                      g.bias, g.in_fin, g.colsum, g.M, g.N, g.K, lens, scale)

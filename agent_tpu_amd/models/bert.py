@@ -228,6 +228,11 @@ class BertClassifier:
         self.ln_fold = (self.device.type == "cuda" and not fp32
                         and os.getenv("ATPU_LN_FOLD", "1") not in ("0", "false", "no"))
         self._folded: Optional[Dict[str, torch.Tensor]] = None
+        # activations between the folded encoder's GEMMs in K-tile image order (ops.to_image_order):
+        # ATPU_ACT_LAYOUT=1 the FFN intermediate, 2 also the attention context, 3 (default) also
+        # the hidden states between full layers (layer 0's input and the last full layer's output
+        # stay row-major); 0 everything row-major. Logits are bit-identical at every level.
+        self.act_layout = int(os.getenv("ATPU_ACT_LAYOUT", "3") or 0)
         # QKV projection + attention fused into one kernel (S = 128, LN-folded encoder):
         # ATPU_QKV_ATTN=0 runs the QKV GEMM and the packed attention kernel separately
         self.fused_qkv_attention = os.getenv("ATPU_QKV_ATTN", "1") not in ("0", "false", "no")
@@ -308,27 +313,40 @@ class BertClassifier:
         last_full = cfg.layers - 1 if cls_only_last else cfg.layers
         fused = self.fused_qkv_attention and ops.qkv_attention_ok(M, 3 * H, H, S) and cfg.head_dim == 64
         g = h0
+        # which tensors lie in K-tile image order (ops.to_image_order; see __init__): the FFN
+        # intermediate, the attention context, the hidden states a / g between full layers
+        lvl = self.act_layout if dev.type == "cuda" and ops.image_order_ok() else 0
+        ffn_i, ctx_i, hid_i = lvl >= 1, lvl >= 2 and fused, lvl >= 3 and fused
+
+        def lay(a=False, c=False, r=False):
+            return (ops.LAYOUT_A if a else 0) | (ops.LAYOUT_C if c else 0) | (ops.LAYOUT_R if r else 0)
+
         for i in range(last_full):
             q = f"l{i}."
             if fused:
                 # QKV projection + attention in one kernel: the [M, 3H] QKV tensor never exists
                 ctx = ops.qkv_attention(g, f[q + "qkv_wh"], f[q + "qkv_bh"], lens, cfg.heads,
-                                        in_fin=fin if i > 0 else None, colsum_h=f.get(q + "qkv_ch") if i > 0 else None)
+                                        in_fin=fin if i > 0 else None, colsum_h=f.get(q + "qkv_ch") if i > 0 else None,
+                                        layout=lay(a=hid_i and i > 0, c=ctx_i))
             else:
                 if i == 0:
                     qkv = ops.linear(h0, p[q + "qkv_w"], p[q + "qkv_b"])
                 else:  # consumes LN2_{i-1}(g); fin = its statistics (also the out-proj residual's)
                     qkv = ops.linear_ln(g, f[q + "qkv_w"], f[q + "qkv_b"], in_fin=fin, colsum=f[q + "qkv_c"])
                 ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
-            if i == 0:
-                a = ops.linear_ln(ctx, p[q + "o_w"], p[q + "o_b"], residual=h0, part_out=part)
+            if i == 0:  # the residual h0 is row-major
+                a = ops.linear_ln(ctx, p[q + "o_w"], p[q + "o_b"], residual=h0, part_out=part,
+                                  layout=lay(a=ctx_i, c=hid_i))
             else:
                 a = ops.linear_ln(ctx, p[q + "o_w"], f[q + "o_b"], residual=g, res_fin=fin,
-                                  res_gamma=p[f"l{i - 1}.ln2_g"], part_out=part)
+                                  res_gamma=p[f"l{i - 1}.ln2_g"], part_out=part,
+                                  layout=lay(a=ctx_i, c=hid_i, r=hid_i))
             ops.ln_finalize(part, H, eps, out=fin)  # LN1 statistics of a
-            ff = ops.linear_ln(a, f[q + "f1_w"], f[q + "f1_b"], act="gelu", in_fin=fin, colsum=f[q + "f1_c"])
+            ff = ops.linear_ln(a, f[q + "f1_w"], f[q + "f1_b"], act="gelu", in_fin=fin, colsum=f[q + "f1_c"],
+                               layout=lay(a=hid_i, c=ffn_i))
             g = ops.linear_ln(ff, p[q + "f2_w"], f[q + "f2_b"], residual=a, res_fin=fin,
-                              res_gamma=p[q + "ln1_g"], part_out=part)
+                              res_gamma=p[q + "ln1_g"], part_out=part,
+                              layout=lay(a=ffn_i, c=hid_i and i + 1 < last_full, r=hid_i))  # last g: row-major
             ops.ln_finalize(part, H, eps, out=fin)  # LN2 statistics of g
         ln2 = f"l{last_full - 1}."
         if raw:

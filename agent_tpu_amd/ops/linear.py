@@ -345,13 +345,15 @@ def linear_ln(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, act: Opti
               in_fin: Optional[torch.Tensor] = None, colsum: Optional[torch.Tensor] = None,
               residual: Optional[torch.Tensor] = None, res_fin: Optional[torch.Tensor] = None,
               res_gamma: Optional[torch.Tensor] = None, part_out: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, layout: int = 0) -> torch.Tensor:
     """Linear layer of a LayerNorm-folded encoder (see the block comment above).
 
     * ``in_fin [M, 2]`` (+ ``colsum``): ``x`` holds raw LN inputs whose (rstd, rstd*mu)
       are ``in_fin``; ``w``/``bias`` are folded (:func:`fold_ln_into_linear`).
     * ``res_fin`` + ``res_gamma``: ``residual`` holds raw LN inputs; the bias carries beta.
     * ``part_out [N/256, M, 2]``: row partials of the output (fp32, before bf16 rounding).
+    * ``layout`` (GPU only; ``LAYOUT_A | LAYOUT_C | LAYOUT_R``): ``x`` / the output / ``residual`` lie
+      in K-tile image order (:func:`to_image_order`) instead of row-major; plain bias is allowed then.
     """
     in_norm, res_norm = in_fin is not None, res_fin is not None
     check(act in (None, "gelu"), f"linear_ln: activation {act!r} not supported")
@@ -361,6 +363,7 @@ def linear_ln(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, act: Opti
     M, K = x.shape
     N = w.shape[0]
     if not x.is_cuda:
+        check(layout == 0, "linear_ln: image-order operands exist on the GPU path only")
         y = x.float() @ w.float().t()
         if in_norm:
             y = y * in_fin[:, :1] - in_fin[:, 1:] * colsum.float().unsqueeze(0)
@@ -406,12 +409,40 @@ def linear_ln(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, act: Opti
         f32(part_out, (N // 256, M, 2), "part_out")
         epi |= EPI_STATS_OUT
     check(epi in (EPI_BIAS | EPI_IN_NORM, EPI_BIAS | EPI_IN_NORM | EPI_GELU,
-                  EPI_BIAS | EPI_RESIDUAL | EPI_STATS_OUT, EPI_BIAS | EPI_RESIDUAL | EPI_RES_NORM | EPI_STATS_OUT),
+                  EPI_BIAS | EPI_RESIDUAL | EPI_STATS_OUT, EPI_BIAS | EPI_RESIDUAL | EPI_RES_NORM | EPI_STATS_OUT)
+          or (layout and epi == EPI_BIAS),
           f"linear_ln: unsupported epilogue combination {epi}")
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     check(tuple(out.shape) == (M, N) and out.dtype == torch.bfloat16, "out must be bf16 [M, N]")
     native().gemm_ln(ptr(x), row_stride(x, "x"), ptr(w), row_stride(w, "w"), ptr(out), row_stride(out, "out"),
                      ptr(bias), ptr(residual), ldr, M, N, K, epi, ptr(in_fin), ptr(colsum), ptr(res_fin),
-                     ptr(res_gamma), ptr(part_out), launch_stream(x))
+                     ptr(res_gamma), ptr(part_out), launch_stream(x), layout)
     return out
+
+
+# operand bits of ``linear_ln(layout=...)``
+LAYOUT_A, LAYOUT_C, LAYOUT_R = 1, 2, 4
+
+
+def image_order_ok() -> bool:
+    """The GEMM build takes image-order operands: the default persistent 256x256 kernel, no forced tile."""
+    try:
+        return native().gemm_256_variant(-1) == 4 and native().gemm_force_tile(-1) == 0
+    except Exception:
+        return False
+
+
+def to_image_order(x: torch.Tensor) -> torch.Tensor:
+    """Row-major ``[M, W]`` -> K-tile image order ``[M/256][W/64][256][64]`` (same shape and storage size):
+    each 256-row x 64-column block contiguous, which is one K-tile of a consuming 256x256 GEMM."""
+    M, W = x.shape
+    check(M % 256 == 0 and W % 64 == 0, "image order needs M % 256 == 0 and W % 64 == 0")
+    return x.reshape(M // 256, 256, W // 64, 64).permute(0, 2, 1, 3).contiguous().view(M, W)
+
+
+def from_image_order(x: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`to_image_order`."""
+    M, W = x.shape
+    check(M % 256 == 0 and W % 64 == 0, "image order needs M % 256 == 0 and W % 64 == 0")
+    return x.reshape(M // 256, W // 64, 256, 64).permute(0, 2, 1, 3).contiguous().view(M, W)

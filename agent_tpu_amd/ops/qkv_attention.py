@@ -45,13 +45,15 @@ def qkv_attention_ok(M: int, N: int, K: int, S: int) -> bool:
 
 def qkv_attention(x: torch.Tensor, w_h: torch.Tensor, b_h: torch.Tensor, lens: torch.Tensor, heads: int, *,
                   in_fin: Optional[torch.Tensor] = None, colsum_h: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                  layout: int = 0) -> torch.Tensor:
     """Context ``[M, heads*64]`` of BERT self-attention over ``x [M, K]`` (M = B * 128 rows).
 
     ``w_h [3*heads*64, K]`` / ``b_h`` / ``colsum_h``: the QKV projection in head order
     (:func:`qkv_head_order`). ``in_fin [M, 2]`` + ``colsum_h``: ``x`` holds raw LayerNorm
     inputs and the weights are folded (:func:`ops.fold_ln_into_linear`), as ``linear_ln``.
-    Keys ``>= lens[b]`` are masked."""
+    Keys ``>= lens[b]`` are masked. ``layout`` (GPU only): ``ops.LAYOUT_A`` / ``ops.LAYOUT_C``, ``x`` /
+    the context in K-tile image order (:func:`ops.to_image_order`)."""
     scale = 1.0 / math.sqrt(HEAD_DIM) if scale is None else float(scale)
     M, K = x.shape
     N = w_h.shape[0]
@@ -60,6 +62,7 @@ def qkv_attention(x: torch.Tensor, w_h: torch.Tensor, b_h: torch.Tensor, lens: t
     check(M % SEQ == 0, "qkv_attention: rows must be B * 128")
     B = M // SEQ
     if not x.is_cuda:
+        check(layout == 0, "qkv_attention: image-order operands exist on the GPU path only")
         inv = torch.argsort(qkv_head_order(heads))
         y = x.float() @ w_h.float().t()
         if in_fin is not None:
@@ -85,5 +88,6 @@ def qkv_attention(x: torch.Tensor, w_h: torch.Tensor, b_h: torch.Tensor, lens: t
     check(out.dtype == torch.bfloat16 and tuple(out.shape) == (M, hd) and out.stride(1) == 1
           and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0, "out must be bf16 [M, heads*64], 16-B rows")
     native().qkv_attention(ptr(x), row_stride(x, "x"), ptr(w_h), row_stride(w_h, "w_h"), ptr(out), out.stride(0),
-                           ptr(b_h), M, N, K, epi, ptr(in_fin), ptr(colsum_h), ptr(lens), scale, launch_stream(x))
+                           ptr(b_h), M, N, K, epi, ptr(in_fin), ptr(colsum_h), ptr(lens), scale, launch_stream(x),
+                           layout)
     return out
