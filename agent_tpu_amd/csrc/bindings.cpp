@@ -242,6 +242,16 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("q"), py::arg("c"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("k"),
       py::arg("P"), py::arg("stream"));
   m.def(
+      "sim_topk_partial_f16",
+      [](uintptr_t q, uintptr_t c, uintptr_t row_scale, uintptr_t ws, int nq, int N, int D, int k, int splits,
+         uintptr_t stream) {
+        sim_topk_partial_f16(P<const float>(q), P<const _Float16>(c), P<const float>(row_scale), P<float>(ws), nq, N, D,
+                             k, splits, S(stream));
+      },
+      "sim_topk_partial over a float16 corpus, the fp32 score times row_scale [N] (0 = none) before the ranking",
+      py::arg("q"), py::arg("c"), py::arg("row_scale"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"),
+      py::arg("k"), py::arg("P"), py::arg("stream"));
+  m.def(
       "sim_topk_merge",
       [](uintptr_t ws, uintptr_t scores, uintptr_t ids, int nq, int splits, int k, int kk, int64_t id_base,
          uintptr_t stream) {

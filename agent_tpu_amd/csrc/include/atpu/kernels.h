@@ -142,6 +142,12 @@ void sim_topk_partial(const float* q, const float* c, float* ws, int nq, int N, 
                       hipStream_t stream);
 void sim_topk_merge(const float* ws, float* scores, int64_t* ids, int nq, int P, int k, int kk, int64_t id_base,
                     hipStream_t stream);
+// The same over a float16 corpus c [N, D] (sim_topk_f16.hip): every score is the exact fp32 dot
+// product of q and the widened stored values, times row_scale[row] (fp32 [N], or nullptr) before
+// the ranking. Same shapes, workspace and merge; its k order is its own (a function of D alone).
+// Nothing outside c[0:N] and row_scale[0:N] is read.
+void sim_topk_partial_f16(const float* q, const _Float16* c, const float* row_scale, float* ws, int nq, int N, int D,
+                          int k, int P, hipStream_t stream);
 
 // ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
 // Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),

@@ -1,4 +1,4 @@
-"""Top-k similarity search over fp32 vectors: a GEMM whose score matrix is never written.
+"""Top-k similarity search over fp32 or fp16 vectors: a GEMM whose score matrix is never written.
 
 ``sim_topk`` (``csrc/kernels/sim_topk.hip``) returns, for every query row of ``q [nq, D]``, the
 ``kk = min(k, N)`` rows of the corpus ``c [N, D]`` with the largest dot product:
@@ -13,6 +13,15 @@ Every (query, row) score is ONE fp32 accumulator fed by the exact f32 MFMA in a 
 depends on ``D`` alone, and the corpus splits' partial lists ``[nq, P, k]`` merge in the same
 total order, so the result has the same bits for every ``splits`` value and every query batch.
 ``splits=None`` picks ``P`` from ``N`` and the CU count; the argument exists for tests and benches.
+
+A ``float16`` corpus (``csrc/kernels/sim_topk_f16.hip``) keeps all of that at half the bytes: an
+fp16 value widens to fp32 exactly, so the score is the exact fp32 dot product of ``q`` and the
+stored values, fed to the same MFMA. An optional fp32 ``row_scale [N]`` multiplies the finished
+accumulator once, before the ranking:
+
+    scores[i, j] = dot(q[i], float(c[r])) * row_scale[r],   r = ids[i, j] - id_base
+
+which is cosine similarity over rows stored as they are (``row_scale = 1 / ||c[r]||``).
 """
 from __future__ import annotations
 
@@ -33,8 +42,8 @@ def sim_topk_ok(D: int, k: int) -> bool:
     return D % 64 == 0 and 64 <= D <= 1024 and 1 <= k <= MAX_K
 
 
-def sim_topk_ref(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, dtype=torch.float32
-                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+def sim_topk_ref(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, dtype=torch.float32,
+                 row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """PyTorch twin in ``dtype`` math -> (scores ``[nq, kk]`` of ``dtype``, ids ``[nq, kk]`` int64); also the
     CPU path. Two stable sorts give the (score desc, id asc) order: ``torch.topk`` promises no tie order."""
     check(q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1], "sim_topk: q [nq, D] and c [N, D]")
@@ -42,6 +51,9 @@ def sim_topk_ref(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, dty
     N = c.shape[0]
     kk = min(k, N)
     s = q.to(dtype) @ c.to(dtype).T  # [nq, N]; columns are already in ascending id
+    if row_scale is not None:
+        check(row_scale.shape == (N,), "sim_topk: row_scale must be [N]")
+        s = s * row_scale.to(dtype)
     order = torch.sort(s + 0.0, dim=1, descending=True, stable=True).indices[:, :kk]  # -0.0 + 0.0 = +0.0: they tie
     return torch.gather(s, 1, order), order.to(torch.int64) + int(id_base)
 
@@ -52,12 +64,21 @@ def auto_splits(N: int, nq: int, device: torch.device) -> int:
     return max(1, min(MAX_SPLITS, cus // ((nq + 31) // 32)))
 
 
-def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits: Optional[int] = None
-             ) -> Tuple[torch.Tensor, torch.Tensor]:
+def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits: Optional[int] = None,
+             row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(scores ``[nq, kk]`` fp32, ids ``[nq, kk]`` int64), ``kk = min(k, N)``, of the contiguous fp32
-    ``q [nq, D]`` against ``c [N, D]``."""
+    ``q [nq, D]`` against the contiguous fp32 or fp16 ``c [N, D]``; ``row_scale`` (fp32 ``[N]``,
+    contiguous) goes with an fp16 ``c`` only."""
     check(q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1], "sim_topk: q [nq, D] and c [N, D]")
-    check(q.dtype == torch.float32 and c.dtype == torch.float32, "sim_topk: q and c must be fp32")
+    check(q.dtype == torch.float32 and c.dtype in (torch.float32, torch.float16),
+          "sim_topk: q must be fp32 and c fp32 or fp16")
+    half = c.dtype == torch.float16
+    check(row_scale is None or half, "sim_topk: row_scale needs an fp16 c")
+    if row_scale is not None:
+        check(isinstance(row_scale, torch.Tensor) and row_scale.dtype == torch.float32
+              and row_scale.shape == (c.shape[0],) and row_scale.is_contiguous(),
+              "sim_topk: row_scale must be a contiguous fp32 [N]")
+        same_device(c, row_scale)
     check(isinstance(k, int) and not isinstance(k, bool), "sim_topk: k must be an int")
     nq, D = q.shape
     N = c.shape[0]
@@ -72,13 +93,17 @@ def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits:
         return (torch.empty((0, kk), dtype=torch.float32, device=q.device),
                 torch.empty((0, kk), dtype=torch.int64, device=q.device))
     if not q.is_cuda:
-        return sim_topk_ref(q, c, k, id_base)
+        return sim_topk_ref(q, c, k, id_base, row_scale=row_scale)
     nat = native()
     P = nat.sim_topk_splits(N, splits if splits is not None else auto_splits(N, nq, q.device))
     ws = torch.empty((nq, P, k, 2), dtype=torch.float32, device=q.device)
     scores = torch.empty((nq, kk), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, kk), dtype=torch.int64, device=q.device)
     stream = launch_stream(q)
-    nat.sim_topk_partial(ptr(q), ptr(c), ptr(ws), nq, N, D, k, P, stream)
+    if half:
+        nat.sim_topk_partial_f16(ptr(q), ptr(c), ptr(row_scale) if row_scale is not None else 0, ptr(ws), nq, N, D, k,
+                                 P, stream)
+    else:
+        nat.sim_topk_partial(ptr(q), ptr(c), ptr(ws), nq, N, D, k, P, stream)
     nat.sim_topk_merge(ptr(ws), ptr(scores), ptr(ids), nq, P, k, kk, int(id_base), stream)
     return scores, ids

@@ -6,13 +6,17 @@ writes with ``output: "npy"``. :func:`load_corpus` memory-maps it, so a DP rank 
 device for the cosine metric (one-time work per index, not the hot path), refuses non-finite
 values, and keeps the loaded slices in a small LRU keyed by the file's identity (a rewritten file
 misses). :func:`search` is ``ops.sim_topk`` on the GPU and its PyTorch twin on a CPU engine.
+
+With ``dtype="float16"`` the resident rows are fp16 (a ``float16`` file as it is, a ``float32`` file
+rounded to nearest) at half the bytes, and cosine keeps the rows unnormalised beside an fp32
+``row_scale = 1 / max(||row||_2, 1e-12)`` that ``sim_topk`` multiplies into the finished score.
 """
 from __future__ import annotations
 
 import os
 import threading
 from collections import OrderedDict
-from typing import Any, Dict, NamedTuple, Tuple
+from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -25,17 +29,25 @@ ERRORS: Dict[str, str] = {
     "corpus_nonfinite": "corpus holds non-finite values",
     "corpus_too_large": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float32",
 }
+#: those of a ``float16``-resident corpus (``ops/map_search.py``: ``F16_ERRORS``)
+F16_ERRORS: Dict[str, str] = {
+    "corpus_f16_range": "corpus values exceed the float16 range",
+    "corpus_too_large_f16": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float16",
+}
+DTYPES = ("float32", "float16")
+CHUNK_BYTES = 64 * 2 ** 20  # fp32 bytes of the row chunks that a float16 load checks and norms
 
 
 class Corpus(NamedTuple):
-    vectors: torch.Tensor  # [count, dim] fp32 on the device, contiguous
+    vectors: torch.Tensor  # [count, dim] fp32 or fp16 on the device, contiguous
     start: int  # row of the file that vectors[0] is
     total: int  # rows of the whole file
     cached: bool  # served from the LRU
+    scale: Optional[torch.Tensor] = None  # [count] fp32: the cosine row scale of fp16 vectors
 
 
 _lock = threading.Lock()
-_cache: "OrderedDict[Tuple, torch.Tensor]" = OrderedDict()
+_cache: "OrderedDict[Tuple, Tuple[torch.Tensor, Optional[torch.Tensor]]]" = OrderedDict()
 
 
 def lru_capacity() -> int:
@@ -79,36 +91,68 @@ def normalize_rows(x: torch.Tensor) -> torch.Tensor:
     return x / x.norm(dim=1, keepdim=True).clamp_min(EPS)
 
 
-def load_corpus(uri: Any, start: int = 0, count: int = -1, normalize: bool = True,
-                device: torch.device = torch.device("cpu")) -> Corpus:
-    """Rows ``[start, start + count)`` (``count < 0``: to the end) of the file as fp32 on ``device``."""
+def _load_f16(arr, start: int, count: int, normalize: bool, device: torch.device):
+    """-> (fp16 rows ``[count, dim]``, fp32 scale ``[count]`` or None) on ``device``, in row chunks: the
+    finiteness and range checks and the norms never hold an fp32 copy of more than one chunk."""
     import numpy as np
 
+    dim = int(arr.shape[1])
+    vec = torch.empty((count, dim), dtype=torch.float16, device=device)
+    scale = torch.empty((count,), dtype=torch.float32, device=device) if normalize else None
+    rows = max(1, CHUNK_BYTES // (dim * 4))
+    for lo in range(0, count, rows):
+        hi = min(lo + rows, count)
+        src = torch.from_numpy(np.array(arr[start + lo:start + hi], order="C")).to(device)  # only these rows are read
+        if not bool(torch.isfinite(src).all()):
+            raise ValueError(ERRORS["corpus_nonfinite"])
+        part = src.to(torch.float16)  # a float32 file: round to nearest; past the range: inf
+        if not bool(torch.isfinite(part).all()):
+            raise ValueError(F16_ERRORS["corpus_f16_range"])
+        vec[lo:hi] = part
+        if normalize:  # from the resident values; the sum in fp64, so the fp32 scale carries one rounding
+            scale[lo:hi] = part.double().norm(dim=1).clamp_min(EPS).reciprocal().to(torch.float32)
+    return vec, scale
+
+
+def load_corpus(uri: Any, start: int = 0, count: int = -1, normalize: bool = True,
+                device: torch.device = torch.device("cpu"), dtype: str = "float32") -> Corpus:
+    """Rows ``[start, start + count)`` (``count < 0``: to the end) of the file on ``device``: fp32
+    (normalised when ``normalize``), or for ``dtype="float16"`` fp16 as stored plus the fp32 row scale
+    that normalises them."""
+    import numpy as np
+
+    if dtype not in DTYPES:
+        raise ValueError("load_corpus: dtype must be 'float32' or 'float16'")
     arr, path, st = open_corpus(uri)
     total, dim = int(arr.shape[0]), int(arr.shape[1])
     start = max(0, min(int(start), total))
     count = total - start if count < 0 else max(0, min(int(count), total - start))
-    key = (path, st.st_mtime_ns, st.st_size, start, count, bool(normalize), str(device))
+    key = (path, st.st_mtime_ns, st.st_size, start, count, bool(normalize), str(device), dtype)
     with _lock:
         hit = _cache.get(key)
         if hit is not None:
             _cache.move_to_end(key)
-            return Corpus(hit, start, total, True)
-    if count * dim * 4 > max_bytes():  # before any allocation
-        raise ValueError(ERRORS["corpus_too_large"])
-    host = torch.from_numpy(np.array(arr[start:start + count], order="C"))  # a copy: only this slice is read
-    vec = host.to(device).to(torch.float32)  # float16 is widened once, here
-    if not bool(torch.isfinite(vec).all()):
-        raise ValueError(ERRORS["corpus_nonfinite"])
-    if normalize:
-        vec = normalize_rows(vec)
-    vec = vec.contiguous()
+            return Corpus(hit[0], start, total, True, hit[1])
+    if dtype == "float16":
+        if count * dim * 2 + (count * 4 if normalize else 0) > max_bytes():  # before any allocation
+            raise ValueError(F16_ERRORS["corpus_too_large_f16"])
+        vec, scale = _load_f16(arr, start, count, bool(normalize), device)
+    else:
+        if count * dim * 4 > max_bytes():  # before any allocation
+            raise ValueError(ERRORS["corpus_too_large"])
+        host = torch.from_numpy(np.array(arr[start:start + count], order="C"))  # a copy: only this slice is read
+        vec = host.to(device).to(torch.float32)  # float16 is widened once, here
+        if not bool(torch.isfinite(vec).all()):
+            raise ValueError(ERRORS["corpus_nonfinite"])
+        if normalize:
+            vec = normalize_rows(vec)
+        vec, scale = vec.contiguous(), None
     with _lock:
-        _cache[key] = vec
+        _cache[key] = (vec, scale)
         _cache.move_to_end(key)
         while len(_cache) > lru_capacity():
             _cache.popitem(last=False)
-    return Corpus(vec, start, total, False)
+    return Corpus(vec, start, total, False, scale)
 
 
 def clear_cache() -> None:
@@ -119,13 +163,15 @@ def clear_cache() -> None:
 def cache_info() -> Dict[str, Any]:
     with _lock:
         return {"entries": [k[0] for k in _cache], "capacity": lru_capacity(),
-                "resident_bytes": sum(v.numel() * 4 for v in _cache.values())}
+                "resident_bytes": sum(t.numel() * t.element_size() for v in _cache.values() for t in v
+                                      if t is not None)}
 
 
-def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0
-           ) -> Tuple[torch.Tensor, torch.Tensor]:
+def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0,
+           row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(scores ``[nq, kk]`` fp32, ids ``[nq, kk]`` int64) of the fp32 ``qvecs [nq, dim]`` against
-    ``corpus [rows, dim]`` on the corpus's device, ordered by (score desc, id asc). An empty slice
+    ``corpus [rows, dim]`` (fp32, or fp16 with its optional ``row_scale [rows]``) on the corpus's
+    device, ordered by (score desc, id asc). An empty slice
     (a DP rank beyond the corpus) gives ``kk = 0``. A shape the kernel does not take is an error,
     never a detour through PyTorch."""
     from .. import ops
@@ -135,8 +181,8 @@ def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0
         return (torch.empty((q.shape[0], 0), dtype=torch.float32, device=corpus.device),
                 torch.empty((q.shape[0], 0), dtype=torch.int64, device=corpus.device))
     if not corpus.is_cuda:
-        return ops.sim_topk_ref(q, corpus, k, id_base)
-    return ops.sim_topk(q, corpus, k, id_base)
+        return ops.sim_topk_ref(q, corpus, k, id_base, row_scale=row_scale)
+    return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale)
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:

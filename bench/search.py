@@ -9,6 +9,11 @@ finds it in the 256 MiB Infinity Cache. A and B alternate for ``--rounds`` round
 one JSON line per (N, queries, variant, round): us per call from hipEvents after warm-up, the
 effective corpus rate ``N * D * 4 / t`` in TB/s (for B too: what the same answer costs per corpus
 byte), and TF/s (``2 * queries * N * D / t``). ``--splits`` overrides the automatic split count.
+
+``--corpus-dtype float16`` compares the two corpus kernels instead, on the same values: A is
+``ops.sim_topk(q, c16, k)`` over ``c16 = normalize(randn).half()`` (twice the buffers, so that the
+rotation covers the same bytes), B is ``ops.sim_topk(q, c16.float(), k)``. The corpus rate is then
+that of the bytes actually read (2 or 4 per element).
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ def main() -> int:
     ap.add_argument("--buffers", type=int, default=4)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--corpus-dtype", choices=("float32", "float16"), default="float32")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -42,9 +48,16 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     D, k = a.dim, a.top_k
     gen = torch.Generator(device=dev).manual_seed(0)
+    half = a.corpus_dtype == "float16"
     for N in a.rows:
         nbuf = a.buffers if N * D * 4 < 512 * 2 ** 20 else 1
         cs = [torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=gen), dim=1) for _ in range(nbuf)]
+        if half:
+            c16 = [c.half() for c in cs]
+            cs = [c.float() for c in c16]
+            if nbuf > 1:
+                c16 += [torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=gen), dim=1).half()
+                        for _ in range(nbuf)]
         for nq in a.queries:
             q = torch.nn.functional.normalize(torch.randn(nq, D, device=dev, generator=gen), dim=1)
 
@@ -54,28 +67,37 @@ def main() -> int:
             def partner(i):
                 return torch.topk(q @ cs[i].T, k)
 
-            def timed(fn):
-                for i in range(max(nbuf, 2)):
-                    fn(i % nbuf)
+            def fused16(i):
+                return ops.sim_topk(q, c16[i], k, splits=a.splits or None)
+
+            def timed(fn, nb):
+                for i in range(max(nb, 2)):
+                    fn(i % nb)
                 torch.cuda.synchronize(dev)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 for it in range(a.iters):
-                    fn(it % nbuf)
+                    fn(it % nb)
                 e1.record()
                 torch.cuda.synchronize(dev)
                 return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
 
-            same = torch.equal(fused(0)[1], partner(0)[1])  # random data: no ties expected
+            if half:  # (variant, call, buffers it rotates through, bytes per corpus element)
+                variants = (("sim_topk_f16", fused16, len(c16), 2), ("sim_topk_f32_same_values", fused, nbuf, 4))
+            else:
+                variants = (("sim_topk", fused, nbuf, 4), ("torch_matmul_topk", partner, nbuf, 4))
+            same = torch.equal(variants[0][1](0)[1], variants[1][1](0)[1])  # random data: no ties expected
             for r in range(a.rounds):
-                for variant, fn in (("sim_topk", fused), ("torch_matmul_topk", partner)):
-                    us = timed(fn)
+                for variant, fn, nb, size in variants:
+                    us = timed(fn, nb)
                     print(json.dumps({"bench": "search", "variant": variant, "N": N, "queries": nq, "dim": D, "top_k": k,
                                       "round": r, "us_per_call": round(us, 2),
-                                      "corpus_tbs": round(N * D * 4 / us / 1e6, 3),
+                                      "corpus_tbs": round(N * D * size / us / 1e6, 3),
                                       "tflops": round(2.0 * nq * N * D / us / 1e6, 2),
                                       "ids_equal_between_variants": same}), flush=True)
         del cs
+        if half:
+            del c16
     return 0
 
 

@@ -13,6 +13,7 @@ merges the per-rank lists in the same total order (score descending, id ascendin
 from __future__ import annotations
 
 import math
+import os
 import time
 from typing import Any, Dict, List, NamedTuple, Optional
 
@@ -39,6 +40,14 @@ ERRORS: Dict[str, str] = {
     "dim": "corpus dim differs from the query dim (the model's hidden size or the query_vectors' length)",
     "corpus_too_large": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float32",
 }
+#: those of ``corpus_dtype`` and of a float16-resident corpus (also in the contract)
+F16_ERRORS: Dict[str, str] = {
+    "corpus_dtype": "payload.corpus_dtype must be 'float32' or 'float16'",
+    "corpus_dtype_env": "SEARCH_INDEX_DTYPE must be 'float32' or 'float16'",
+    "corpus_f16_range": "corpus values exceed the float16 range",
+    "corpus_too_large_f16": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float16",
+}
+CORPUS_DTYPES = ("float32", "float16")
 
 
 class Options(NamedTuple):
@@ -46,6 +55,7 @@ class Options(NamedTuple):
     metric: str
     pooling: str
     min_score: Optional[float]
+    corpus_dtype: str = "float32"  # residency of a corpus_uri corpus on the device
 
 
 def _number(x: Any) -> bool:
@@ -66,7 +76,15 @@ def options(payload: Dict[str, Any]) -> Options:
     min_score = payload.get("min_score")
     if min_score is not None and not _number(min_score):
         raise ValueError(ERRORS["min_score"])
-    return Options(top_k, metric, pooling, None if min_score is None else float(min_score))
+    if "corpus_dtype" in payload:  # the payload wins: the environment is not looked at
+        corpus_dtype = payload["corpus_dtype"]
+        if corpus_dtype not in CORPUS_DTYPES:
+            raise ValueError(F16_ERRORS["corpus_dtype"])
+    else:
+        corpus_dtype = os.getenv("SEARCH_INDEX_DTYPE", "float32")
+        if corpus_dtype not in CORPUS_DTYPES:
+            raise ValueError(F16_ERRORS["corpus_dtype_env"])
+    return Options(top_k, metric, pooling, None if min_score is None else float(min_score), corpus_dtype)
 
 
 def check_payload(payload: Dict[str, Any]) -> Options:
@@ -101,9 +119,10 @@ def _texts(rows: List[Any]) -> List[str]:
 
 
 def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, pooling: str,
-                   rank: int, ws: int):
-    """Every rank: this rank's slice of the corpus searched for all ``qvecs [nq, dim]`` (host or
-    device fp32, already normalised for cosine), the per-rank lists padded to ``top_k``,
+                   rank: int, ws: int, corpus_dtype: str = "float32"):
+    """Every rank: this rank's slice of the corpus (resident as ``corpus_dtype`` in the ``corpus_uri``
+    form) searched for all ``qvecs [nq, dim]`` (host or device fp32, already normalised for
+    cosine), the per-rank lists padded to ``top_k``,
     all-gathered and merged. -> (scores ``[nq, kk]``, ids ``[nq, kk]`` on the host, corpus rows,
     index_cached or None) on rank 0, None elsewhere. Local errors are exchanged before the
     collective, so a bad corpus fails every rank together with the single-process message."""
@@ -114,7 +133,7 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
     from agent_tpu_amd.runtime import search as rs
 
     cosine = metric == "cosine"
-    exc, s, i, total, cached = None, None, None, 0, None
+    exc, s, i, total, cached, scale = None, None, None, 0, None, None
     nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
     try:
         if "corpus_uri" in payload:
@@ -122,8 +141,8 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
             if cdim != dim:
                 raise ValueError(ERRORS["dim"])
             s_r, n_r = split_range(0, total, ws, rank)
-            corpus = rs.load_corpus(payload["corpus_uri"], s_r, n_r, cosine, device)
-            vec, cached = corpus.vectors, corpus.cached
+            corpus = rs.load_corpus(payload["corpus_uri"], s_r, n_r, cosine, device, corpus_dtype)
+            vec, cached, scale = corpus.vectors, corpus.cached, corpus.scale
         else:  # corpus_texts: each rank embeds its slice; ids index the list; nothing is cached
             texts = _texts(payload["corpus_texts"])
             total = len(texts)
@@ -132,7 +151,7 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
             s_r, n_r = split_range(0, total, ws, rank)
             vec = h.engine.embed_texts(texts[s_r:s_r + n_r], pooling, cosine).emb.to(device)
         maybe_inject_fault("search")
-        s, i = rs.search(qvecs, vec, top_k, id_base=s_r)
+        s, i = rs.search(qvecs, vec, top_k, id_base=s_r, row_scale=scale)
         if s.shape[1] < top_k:  # a slice shorter than top_k: pad, so every rank gathers [nq, top_k]
             pad = top_k - s.shape[1]
             s = torch.cat([s, torch.full((nq, pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
@@ -188,6 +207,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         out["dp_world_size"] = ws
     if cached is not None:
         out["index_cached"] = bool(cached)
+    if "corpus_uri" in payload and opt.corpus_dtype != "float32":  # default-path results keep their keys
+        out["corpus_dtype"] = opt.corpus_dtype
     out.update(ids=ids_l, scores=sc_l)
     return out
 
@@ -218,7 +239,7 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         qv = torch.zeros((0, dim), dtype=torch.float32) if h is not None else None
         if qv is None:
             raise ValueError(ERRORS["query_vectors"])
-    got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws)
+    got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype)
     if got is None:
         return None
     s, i, total, cached = got
@@ -226,8 +247,9 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
 
 
 def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional[List[Any]]:
-    """The ``queries`` + ``corpus_uri`` jobs of one lease that share (model, pooling, metric, corpus) as
-    one engine call (every rank calls it): one embed of the concatenated queries, one search at the
+    """The ``queries`` + ``corpus_uri`` jobs of one lease that share (model, pooling, metric, corpus,
+    corpus_dtype) as one engine call (every rank calls it): one embed of the concatenated queries,
+    one search at the
     group's largest ``top_k``; each job takes the first ``top_k`` entries of its own rows."""
     out: List[Any] = [None] * len(payloads)
     jobs = []
@@ -251,7 +273,7 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 import torch
 
                 qv = torch.cat([h.engine.embed_texts(ts, key.pooling, key.metric == "cosine").emb for _, _, ts in jobs])
-            got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws)
+            got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
                 out[n] = ("err", exc)
@@ -269,7 +291,8 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 @register_batch_op("map_search")
 def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``queries`` + ``corpus_uri`` jobs that share (model_path, pooling, metric,
-    corpus_uri) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed
+    corpus_uri, corpus_dtype) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs
+    and malformed
     payloads take the single-job path."""
     from agent_tpu_amd.parallel.dp_ops import dispatch
 
@@ -282,7 +305,8 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
             if "queries" not in p or "corpus_uri" not in p:
                 raise KeyError("queries")
             opt = check_payload(p)
-            groups.setdefault((p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"]), []).append(n)
+            groups.setdefault((p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype),
+                              []).append(n)
         except Exception:
             try:
                 out[n] = ("ok", run(p))
