@@ -52,6 +52,10 @@ enum GemmEpilogue : int {
 
 // GemmArgs::layout bits
 constexpr int kLayA = 1, kLayC = 2, kLayR = 4;
+// fragment order (set WITH the operand's image bit, = that bit << 3): the 16-byte units inside
+// each image re-ordered so that one lane's packed accumulator fragment is a unit
+constexpr int kLayFragA = 8, kLayFragC = 16, kLayFragR = 32;
+static_assert(kLayFragA == kLayA << 3 && kLayFragC == kLayC << 3 && kLayFragR == kLayR << 3, "frag bit = image bit << 3");
 
 struct GemmArgs {
   const bf16* A = nullptr;  // [M, K] row-major, leading dim lda
@@ -71,6 +75,11 @@ struct GemmArgs {
   // operand and the 64 columns one wave of the producing GEMM writes. 0 = row-major.
   // Persistent full-line 256x256 kernel (M, N % 256 == 0) and the fused QKV + attention
   // kernel (A, and C = the context: head h of a 2-sequence tile is image h of its row tile).
+  // Fragment order (kLayFragA / C / R with the image bit; A of both kernels, C and R of the GEMM):
+  // same images, inside one [16 row groups of 16 rows][2 k-halves of 32 columns][64 units of
+  // 16 B]; unit u = row u % 16 of the group, columns ([0,2,1,3][u / 16]) * 8 .. + 7 of the half:
+  // what lane u holds after v_permlane16_swap of its packed fragments (j0, j1) or (j2, j3). The
+  // producer stores it without an LDS transpose, the consumer's LDS image is a verbatim copy.
   int layout = 0;
   // split-K (skinny M): splits > 1 needs ws = fp32 [splits, M, N]
   int splits = 1;

@@ -752,12 +752,27 @@ __device__ __forceinline__ size_t img_row0(int m0, int n0, int wm, int wn, int W
   return ((size_t)(m0 >> 8) * (W >> 6) + (n0 >> 6) + wn) * 256 + wm * 128;
 }
 
+// v_permlane16_swap of two dword pairs: lane rows (16 lanes) 1, 3 of x trade places with rows
+// 0, 2 of y. On the packed bf16 pairs of fragments j (x) and j+1 (y), lane (fr, fc) holding
+// columns fc*4..+3 of each, it leaves lane row G with 8 consecutive columns of fragment
+// j + (G & 1): columns (G >> 1)*8..+7. The s_nop covers the VALU-write -> permlane-read hazard.
+__device__ __forceinline__ void swap16x2(unsigned& x0, unsigned& x1, unsigned& y0, unsigned& y1) {
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3"
+               : "+v"(x0), "+v"(x1), "+v"(y0), "+v"(y1));
+}
+
 // IN_ACC (InNorm): the caller started the accumulators at -mu*colsum (else the
 // epilogue applies -rstd*mu*colsum itself, from LDS colsum)
 // NOST (timing-only ablation, results WRONG): the output values are computed but not stored
 // LAY (kLayC / kLayR bits): C / R in K-tile image order [M/256][W/64][256][64] (W = ldc / ldr):
 // the wave's 128 x 64 block is rows wm*128.. of image (m0/256, n0/64 + wn), 128-B rows, so
 // every store / residual load instruction covers 1 KiB contiguous; same instruction count
+// LAY (kLayFragC / kLayFragR with the image bit): C / R in fragment order (GemmArgs::layout).
+// A 16-row block of the wave is then 2 x 64 units of 16 B, unit `lane` of k-half h being what
+// the lane holds after swap16x2 of its packed fragments (2h, 2h+1): the same two 1 KiB
+// instructions per block at the same addresses (block + h*1024 + lane*16), and no LDS
+// transpose: output packed -> swapped -> stored, residual loaded -> swapped (the swap is an
+// involution) -> added per fragment, the same FMAs in the same order
 template <int EPI, bool NT, bool IN_ACC = true, int GM = 0, bool NOST = false, int LAY = 0>
 __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int m0, int n0, int wm, int wn, int lane,
                                                   bf16* __restrict__ C, int ldc, const bf16* __restrict__ R, int ldr,
@@ -793,6 +808,8 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
   const size_t row0 = (size_t)(m0 + wm * 128);
   const int col = n0 + wn * 64 + lc * 8;
   constexpr bool kCImg = LAY & kLayC, kRImg = LAY & kLayR;
+  constexpr bool kCFrag = LAY & kLayFragC, kRFrag = LAY & kLayFragR;
+  static_assert((!kCFrag || kCImg) && (!kRFrag || kRImg), "fragment order lives inside image order");
   // image order = a row-major [*, 64] array whose row 0 is the image's first row
   const size_t crow0 = kCImg ? img_row0(m0, n0, wm, wn, ldc) : row0;
   const size_t rrow0 = kRImg ? img_row0(m0, n0, wm, wn, ldr) : row0;
@@ -866,11 +883,25 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
       // every earlier block added its 2 stores -> 14 for every i
       asm volatile("s_waitcnt vmcnt(%2)" : "+v"(res[i][0]), "+v"(res[i][1]) : "n"(kResWait) : "memory");
       __builtin_amdgcn_sched_barrier(0);
-      *reinterpret_cast<u32x4*>(scratch + line_off0) = res[i][0];
-      *reinterpret_cast<u32x4*>(scratch + line_off1) = res[i][1];
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      u32x2 rf[4];  // fragment j's 4 columns of the lane's row
+      if constexpr (kRFrag) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          unsigned x0 = res[i][h][0], x1 = res[i][h][1], y0 = res[i][h][2], y1 = res[i][h][3];
+          swap16x2(x0, x1, y0, y1);
+          rf[2 * h] = u32x2{x0, x1};
+          rf[2 * h + 1] = u32x2{y0, y1};
+        }
+      } else {
+        *reinterpret_cast<u32x4*>(scratch + line_off0) = res[i][0];
+        *reinterpret_cast<u32x4*>(scratch + line_off1) = res[i][1];
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const bf16x4 r = *reinterpret_cast<const bf16x4*>(scratch + frag_off(j));
+        bf16x4 r;
+        if constexpr (kRFrag) r = __builtin_bit_cast(bf16x4, rf[j]);
+        else r = *reinterpret_cast<const bf16x4*>(scratch + frag_off(j));
         if constexpr (kRes) {
           // residual = LN(r) = (r*rstd - rstd*mu) * gamma (+ beta, folded into the bias)
 #pragma unroll
@@ -902,14 +933,29 @@ __device__ __forceinline__ void epilogue_256_line(const f32x4 (&acc)[8][4], int 
       const f32x2 s = f32x2{sum_lane_rows(s1[0] + s1[1]), sum_lane_rows(s2[0] + s2[1])};
       if (fc == 0) *reinterpret_cast<f32x2*>(ln.st + (wn * 256 + lrow) * 2) = s;
     }
+    u32x4 o0, o1;
+    if constexpr (kCFrag) {
+      // the lane's two units of the block, one per k-half: no scratch
+      unsigned p[4][2];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const unsigned p0 = pack_bf16x2(v[j][0], v[j][1]), p1 = pack_bf16x2(v[j][2], v[j][3]);
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-      *reinterpret_cast<u32x2*>(scratch + frag_off(j)) = u32x2{p0, p1};
+      for (int j = 0; j < 4; ++j) {
+        p[j][0] = pack_bf16x2(v[j][0], v[j][1]);
+        p[j][1] = pack_bf16x2(v[j][2], v[j][3]);
+      }
+      swap16x2(p[0][0], p[0][1], p[1][0], p[1][1]);
+      swap16x2(p[2][0], p[2][1], p[3][0], p[3][1]);
+      o0 = u32x4{p[0][0], p[0][1], p[1][0], p[1][1]};
+      o1 = u32x4{p[2][0], p[2][1], p[3][0], p[3][1]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned p0 = pack_bf16x2(v[j][0], v[j][1]), p1 = pack_bf16x2(v[j][2], v[j][3]);
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        *reinterpret_cast<u32x2*>(scratch + frag_off(j)) = u32x2{p0, p1};
+      }
+      o0 = *reinterpret_cast<const u32x4*>(scratch + line_off0);
+      o1 = *reinterpret_cast<const u32x4*>(scratch + line_off1);
     }
-    const u32x4 o0 = *reinterpret_cast<const u32x4*>(scratch + line_off0);
-    const u32x4 o1 = *reinterpret_cast<const u32x4*>(scratch + line_off1);
     u32x4* cp = reinterpret_cast<u32x4*>(C + (crow0 + i * 16 + lr) * cld + ccol);
     u32x4* cp1 = reinterpret_cast<u32x4*>(C + (crow0 + i * 16 + lr + 8) * cld + ccol);
     if constexpr (NOST) {
@@ -950,7 +996,9 @@ struct LnFold {
   float* part_out;
 };
 
-// DBG (timing-only ablation, results WRONG): 1 = skip the epilogue (acc kept live)
+// DBG (timing-only ablation, results WRONG): 1 = skip the epilogue (acc kept live); 512 = the
+// line epilogue without its LDS transposes (see the epilogue call). No library entry point
+// dispatches a DBG build: tools/gemm_ablate.py compiles this file into a library of its own.
 //
 // LayerNorm folding (EPI & (kEpiInNorm | kEpiResNorm | kEpiStatsOut), LINE only, K >= 256):
 //  * K-tile 1, phase 0: the tile's per-row / per-column LN data is staged by 4-byte
@@ -983,6 +1031,12 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
   // A in K-tile image order (lda = K): K-tile kt of row tile tm0 is the contiguous 32 KB image
   // (tm0/256)*(K/64) + kt, its rows 128 B apart: a DMA piece (8 rows) is 1 KiB contiguous
   constexpr bool kAImg = LAY & kLayA;
+  // A in fragment order (GemmArgs::layout): the LDS A image is a verbatim copy of the K-tile's
+  // 32 KiB; a DMA piece is (row group, k-half), 1 KiB copied linearly (source piece + lane*16,
+  // no source swizzle), and the fragment read of lane (fr, fc) for k-step ks is unit
+  // [0,2,1,3][fc]*16 + fr of piece (group, ks): 256 contiguous bytes per 16 lanes
+  constexpr bool kAFrag = LAY & kLayFragA;
+  static_assert(!kAFrag || kAImg, "fragment order lives inside image order");
   static_assert(!(kIn && (kRes || kSt)), "InNorm and ResNorm/StatsOut do not share one kernel (LDS budget)");
   constexpr int kXOff = kEpiOff + (LINE ? 8 * 2048 : 0);
   constexpr int kFinOff = kXOff;                                    // [2 tiles (InNorm)][256][2] (rstd, rstd*mu)
@@ -1007,11 +1061,18 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
     return (q == 0 || q == 3) ? (ql & 63) + (ql >> 6) * 128 + (q == 3 ? 64 : 0)
                               : (ql & 31) + (ql >> 5) * 64 + (q == 2 ? 32 : 0);
   };
+  // fragment-order A: byte offset in the image of piece p (0..15) of quarter q (0 or 3): the
+  // quarter's row groups {0-3, 8-11} (+4 for q 3), both k-halves of a group adjacent
+  auto fpiece = [&](int q, int p) {
+    return (((p >> 1) & 3) + (p >> 3) * 8 + (q == 3 ? 4 : 0)) * 2048 + (p & 1) * 1024;
+  };
   int dst[4][2];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
-    for (int i = 0; i < 2; ++i) dst[q][i] = (q == 0 || q == 3 ? 0 : kImg) + qrow(q, (i * 8 + wave) * 8) * 128;
+    for (int i = 0; i < 2; ++i)
+      dst[q][i] = (kAFrag && (q == 0 || q == 3)) ? fpiece(q, i * 8 + wave)
+                                                 : (q == 0 || q == 3 ? 0 : kImg) + qrow(q, (i * 8 + wave) * 8) * 128;
   // lane ids are made opaque per use (recomputed by mbcnt, never hoisted): with the
   // LayerNorm-folding epilogues the per-lane staging rows kept live across the tile
   // loop spilled, and a scratch reload is a VMEM load the waitcnt pass drains the
@@ -1051,7 +1112,8 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
       for (int i = 0; i < 2; ++i) {
         const int r = qrow(q, (i * 8 + wave) * 8 + (ln >> 3));
         const size_t e = (q == 0 || q == 3)
-                             ? (kAImg ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + sw(r, ln & 7) * 8
+                             ? (kAFrag ? (size_t)(tm0 >> 8) * K * 256 + fpiece(q, i * 8 + wave) / 2 + ln * 8
+                                : kAImg ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + sw(r, ln & 7) * 8
                                       : (size_t)min(tm0 + r, M - 1) * lda + sw(r, ln & 7) * 8)
                              : (size_t)(tn0 + r) * ldb + sw(r, ln & 7) * 8;
         if constexpr (kFold) soff[q][i] = (uint32_t)(e * 2);
@@ -1080,8 +1142,13 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int r = wm * 128 + qm * 64 + i * 16 + fr;
-        af[ks][i] = *reinterpret_cast<const bf16x8*>(img + r * 128 + sw(r, ks * 4 + fc) * 16);
+        if constexpr (kAFrag) {
+          const int unit = (((fc & 1) << 1) | (fc >> 1)) * 16 + fr;  // [0,2,1,3][fc]*16 + fr
+          af[ks][i] = *reinterpret_cast<const bf16x8*>(img + (wm * 8 + qm * 4 + i) * 2048 + ks * 1024 + unit * 16);
+        } else {
+          const int r = wm * 128 + qm * 64 + i * 16 + fr;
+          af[ks][i] = *reinterpret_cast<const bf16x8*>(img + r * 128 + sw(r, ks * 4 + fc) * 16);
+        }
       }
   };
   auto read_b = [&](bf16x8 (&f)[2][2], int buf, int qn) {
@@ -1341,8 +1408,12 @@ __global__ __launch_bounds__(512, 1) void gemm256s_kernel(
       // tile-loop structure, the plain epilogue (no LN math, no statistics)
       constexpr int kEpiRun0 = kBiasAcc ? (EPI & ~kEpiBias) : EPI;
       constexpr int kEpiRun = (DBG & 8) ? (kEpiRun0 & ~(kEpiInNorm | kEpiResNorm | kEpiStatsOut)) : kEpiRun0;
+      // DBG & 512 (timing-only bound of the fragment-order epilogue, results WRONG): the
+      // image-order C / R of this instantiation go through the fragment-order paths (no
+      // scratch round trip, same addresses) while their consumers still read image order
+      constexpr int kLayEpi = (DBG & 512) ? (LAY | ((LAY & (kLayC | kLayR)) << 3)) : LAY;
       if constexpr (LINE)
-        epilogue_256_line<kEpiRun, NT, kInAcc, ((DBG >> 5) & 3), bool(DBG & 256), LAY>(
+        epilogue_256_line<kEpiRun, NT, kInAcc, ((DBG >> 5) & 3), bool(DBG & 256), kLayEpi>(
             acc, cm0, cn0, wm, wn, (kIn || kRes || kSt) ? opaque_lane() : lane, C, ldc, R, ldr,
             reinterpret_cast<const float*>(lds + kBiasOff) + tile_par * 256, lds + kEpiOff + wave * 2048, pre,
             LnLds{reinterpret_cast<const float*>(lds + kFinOff + (kInAcc ? tile_par * 2048 : 0)),
@@ -1439,6 +1510,18 @@ void launch_256s(const GemmArgs& g, hipStream_t s) {
       ATPU_G256S_LAY(kEpiBias, kLayA)
       ATPU_G256S_LAY(kEpiBias, kLayC)
       ATPU_G256S_LAY(kEpiBias, kLayA | kLayC)
+      // fragment order (ATPU_ACT_LAYOUT=4): the hidden states and the FFN intermediate; the
+      // attention context (out-proj's A) stays in image order, layer 0's residual and the last
+      // full layer's output row-major
+      constexpr int kFA = kLayA | kLayFragA, kFC = kLayC | kLayFragC, kFR = kLayR | kLayFragR;
+      ATPU_G256S_LAY(kEpiBias | kEpiInNorm | kEpiGelu, kFC)
+      ATPU_G256S_LAY(kEpiBias | kEpiInNorm | kEpiGelu, kFA | kFC)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kLayA | kFR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kLayA | kFC | kFR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kFA | kFR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiResNorm | kEpiStatsOut, kFA | kFC | kFR)
+      ATPU_G256S_LAY(kEpiBias | kEpiResidual | kEpiStatsOut, kLayA | kFC)
+      ATPU_G256S_LAY(kEpiBias, kFA | kFC)
 #undef ATPU_G256S_LAY
       throw std::invalid_argument("atpu: no image-order GEMM for epilogue " + std::to_string(g.epi) + " layout " +
                                   std::to_string(g.layout));
@@ -2646,8 +2729,11 @@ void gemm_bf16(const GemmArgs& g, hipStream_t stream) {
   if (g.layout) {
     // K-tile image order [M/256][W/64][256][64] of A / C / R: the persistent full-line kernel
     // with nt stores only; the leading dimension of such an operand is its width W
-    ATPU_CHECK(!(g.layout & ~(kLayA | kLayC | kLayR)) && gemm_256_variant(-1) == 4 && !forced && g.splits <= 1,
+    ATPU_CHECK(!(g.layout & ~(kLayA | kLayC | kLayR | kLayFragA | kLayFragC | kLayFragR)) &&
+                   gemm_256_variant(-1) == 4 && !forced && g.splits <= 1,
                "gemm: image-order operands need the default 256x256 kernel, no split-K");
+    ATPU_CHECK(!((g.layout >> 3) & ~g.layout & (kLayA | kLayC | kLayR)),
+               "gemm: a fragment-order bit goes with its operand's image-order bit");
     ATPU_CHECK(g.M % 256 == 0 && g.N % 256 == 0, "gemm: image-order operands need M, N % 256 == 0");
     ATPU_CHECK(!(g.layout & kLayA) || g.lda == g.K, "gemm: image-order A needs lda == K");
     ATPU_CHECK(!(g.layout & kLayC) || g.ldc == g.N, "gemm: image-order C needs ldc == N");

@@ -86,12 +86,21 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict
     return l;
   };
   // per (quarter, round): wave-uniform LDS destination and 32-bit byte offset of the lane's source
+  // A in fragment order (kLayFragA, GemmArgs::layout): the LDS A image is a verbatim copy of the
+  // K-tile; piece p (0..15) of quarter q (0 or 3) is (row group, k-half), the quarter's row
+  // groups {0-3, 8-11} (+4 for q 3), copied linearly (source piece + lane*16, no swizzle)
+  constexpr bool kAFrag = LAY & kLayFragA;
+  static_assert(!kAFrag || (LAY & kLayA), "fragment order lives inside image order");
+  auto fpiece = [&](int q, int p) {
+    return (((p >> 1) & 3) + (p >> 3) * 8 + (q == 3 ? 4 : 0)) * 2048 + (p & 1) * 1024;
+  };
   int dst[4][2];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      dst[q][i] = (q == 0 || q == 3 ? 0 : kHImgA) + hq_row(q, (i * 8 + wave) * 8) * 128;
+      dst[q][i] = (kAFrag && (q == 0 || q == 3)) ? fpiece(q, i * 8 + wave)
+                                                 : (q == 0 || q == 3 ? 0 : kHImgA) + hq_row(q, (i * 8 + wave) * 8) * 128;
   uint32_t soff[4][2];
   auto set_src = [&](int tm0, int tn0) {
     const int ln = opaque_lane();
@@ -101,7 +110,8 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict
       for (int i = 0; i < hq_rounds(q); ++i) {
         const int r = hq_row(q, (i * 8 + wave) * 8 + (ln >> 3));
         const size_t e = (q == 0 || q == 3)
-                             ? ((LAY & kLayA) ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + hsw(r, ln & 7) * 8
+                             ? (kAFrag ? (size_t)(tm0 >> 8) * K * 256 + fpiece(q, i * 8 + wave) / 2 + ln * 8
+                                : (LAY & kLayA) ? (size_t)(tm0 >> 8) * K * 256 + r * 64 + hsw(r, ln & 7) * 8
                                               : (size_t)(tm0 + r) * lda + hsw(r, ln & 7) * 8)
                              : (size_t)(tn0 + r) * ldb + hsw(r, ln & 7) * 8;
         soff[q][i] = (uint32_t)(e * 2);
@@ -131,8 +141,14 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(const bf16* __restrict
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int r = wm * 128 + qm * 64 + i * 16 + fr;
-        af[ks][i] = *reinterpret_cast<const bf16x8*>(img + r * 128 + hsw(r, ks * 4 + fc) * 16);
+        if constexpr (kAFrag) {
+          // unit [0,2,1,3][fc]*16 + fr of piece (row group, ks): 256 contiguous bytes per 16 lanes
+          const int unit = (((fc & 1) << 1) | (fc >> 1)) * 16 + fr;
+          af[ks][i] = *reinterpret_cast<const bf16x8*>(img + (wm * 8 + qm * 4 + i) * 2048 + ks * 1024 + unit * 16);
+        } else {
+          const int r = wm * 128 + qm * 64 + i * 16 + fr;
+          af[ks][i] = *reinterpret_cast<const bf16x8*>(img + r * 128 + hsw(r, ks * 4 + fc) * 16);
+        }
       }
   };
   auto read_b01 = [&](int buf) {
@@ -606,7 +622,9 @@ static void launch_256h(const GemmArgs& g, int mode, const int32_t* lens, float 
   int nb = std::min(tiles, num_cus());
   if (nb >= 8) nb &= ~7;
   if (g.layout) {
-    ATPU_CHECK(mode == 2 && !(g.layout & ~(kLayA | kLayC)), "qkv_attention: image order for A and the context only");
+    ATPU_CHECK(mode == 2 && !(g.layout & ~(kLayA | kLayFragA | kLayC)),
+               "qkv_attention: image order for A and the context, fragment order for A only");
+    ATPU_CHECK(!(g.layout & kLayFragA) || (g.layout & kLayA), "qkv_attention: kLayFragA goes with kLayA");
     ATPU_CHECK(!(g.layout & kLayA) || g.lda == g.K, "qkv_attention: image-order A needs lda == K");
     ATPU_CHECK(!(g.layout & kLayC) || g.ldc == g.N / 3, "qkv_attention: image-order context needs ldo == N / 3");
 #define ATPU_GHL(E, L)                                                                                          \
@@ -619,6 +637,7 @@ static void launch_256h(const GemmArgs& g, int mode, const int32_t* lens, float 
     ATPU_GHL(kEpiBias, kLayC)
     ATPU_GHL(kEpiBias | kEpiInNorm, kLayC)
     ATPU_GHL(kEpiBias | kEpiInNorm, kLayA | kLayC)
+    ATPU_GHL(kEpiBias | kEpiInNorm, kLayA | kLayFragA | kLayC)
 #undef ATPU_GHL
     ATPU_CHECK(false, "qkv_attention: no image-order kernel for this epilogue / layout");
   }

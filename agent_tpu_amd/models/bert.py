@@ -229,10 +229,12 @@ class BertClassifier:
                         and os.getenv("ATPU_LN_FOLD", "1") not in ("0", "false", "no"))
         self._folded: Optional[Dict[str, torch.Tensor]] = None
         # activations between the folded encoder's GEMMs in K-tile image order (ops.to_image_order):
-        # ATPU_ACT_LAYOUT=1 the FFN intermediate, 2 also the attention context, 3 (default) also
-        # the hidden states between full layers (layer 0's input and the last full layer's output
-        # stay row-major); 0 everything row-major. Logits are bit-identical at every level.
-        self.act_layout = int(os.getenv("ATPU_ACT_LAYOUT", "3") or 0)
+        # ATPU_ACT_LAYOUT=1 the FFN intermediate, 2 also the attention context, 3 also the hidden
+        # states between full layers (layer 0's input and the last full layer's output stay
+        # row-major); 4 (default) the FFN intermediate and those hidden states in fragment order
+        # instead (ops.to_fragment_order; the context stays in image order); 0 everything
+        # row-major. Logits are bit-identical at every level.
+        self.act_layout = int(os.getenv("ATPU_ACT_LAYOUT", "4") or 0)
         # QKV projection + attention fused into one kernel (S = 128, LN-folded encoder):
         # ATPU_QKV_ATTN=0 runs the QKV GEMM and the packed attention kernel separately
         self.fused_qkv_attention = os.getenv("ATPU_QKV_ATTN", "1") not in ("0", "false", "no")
@@ -317,9 +319,16 @@ class BertClassifier:
         # intermediate, the attention context, the hidden states a / g between full layers
         lvl = self.act_layout if dev.type == "cuda" and ops.image_order_ok() else 0
         ffn_i, ctx_i, hid_i = lvl >= 1, lvl >= 2 and fused, lvl >= 3 and fused
+        # level 4: a, the FFN intermediate and g between full layers in fragment order
+        # (ops.to_fragment_order: written and read without an LDS transpose); the attention
+        # context (written by the attention epilogue) stays in image order
+        frag = lvl >= 4 and fused
+        # per tensor: 0 row-major, 1 image order, 2 fragment order
+        ffn_o, ctx_o, hid_o = ffn_i * (2 if frag else 1), int(ctx_i), hid_i * (2 if frag else 1)
 
-        def lay(a=False, c=False, r=False):
-            return (ops.LAYOUT_A if a else 0) | (ops.LAYOUT_C if c else 0) | (ops.LAYOUT_R if r else 0)
+        def lay(a=0, c=0, r=0):
+            return ((0, ops.LAYOUT_A, ops.LAYOUT_A_FRAG)[a] | (0, ops.LAYOUT_C, ops.LAYOUT_C_FRAG)[c]
+                    | (0, ops.LAYOUT_R, ops.LAYOUT_R_FRAG)[r])
 
         for i in range(last_full):
             q = f"l{i}."
@@ -327,7 +336,7 @@ class BertClassifier:
                 # QKV projection + attention in one kernel: the [M, 3H] QKV tensor never exists
                 ctx = ops.qkv_attention(g, f[q + "qkv_wh"], f[q + "qkv_bh"], lens, cfg.heads,
                                         in_fin=fin if i > 0 else None, colsum_h=f.get(q + "qkv_ch") if i > 0 else None,
-                                        layout=lay(a=hid_i and i > 0, c=ctx_i))
+                                        layout=lay(a=hid_o if i > 0 else 0, c=ctx_o))
             else:
                 if i == 0:
                     qkv = ops.linear(h0, p[q + "qkv_w"], p[q + "qkv_b"])
@@ -336,17 +345,17 @@ class BertClassifier:
                 ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
             if i == 0:  # the residual h0 is row-major
                 a = ops.linear_ln(ctx, p[q + "o_w"], p[q + "o_b"], residual=h0, part_out=part,
-                                  layout=lay(a=ctx_i, c=hid_i))
+                                  layout=lay(a=ctx_o, c=hid_o))
             else:
                 a = ops.linear_ln(ctx, p[q + "o_w"], f[q + "o_b"], residual=g, res_fin=fin,
                                   res_gamma=p[f"l{i - 1}.ln2_g"], part_out=part,
-                                  layout=lay(a=ctx_i, c=hid_i, r=hid_i))
+                                  layout=lay(a=ctx_o, c=hid_o, r=hid_o))
             ops.ln_finalize(part, H, eps, out=fin)  # LN1 statistics of a
             ff = ops.linear_ln(a, f[q + "f1_w"], f[q + "f1_b"], act="gelu", in_fin=fin, colsum=f[q + "f1_c"],
-                               layout=lay(a=hid_i, c=ffn_i))
+                               layout=lay(a=hid_o, c=ffn_o))
             g = ops.linear_ln(ff, p[q + "f2_w"], f[q + "f2_b"], residual=a, res_fin=fin,
                               res_gamma=p[q + "ln1_g"], part_out=part,
-                              layout=lay(a=ffn_i, c=hid_i and i + 1 < last_full, r=hid_i))  # last g: row-major
+                              layout=lay(a=ffn_o, c=hid_o if i + 1 < last_full else 0, r=hid_o))  # last g: row-major
             ops.ln_finalize(part, H, eps, out=fin)  # LN2 statistics of g
         ln2 = f"l{last_full - 1}."
         if raw:

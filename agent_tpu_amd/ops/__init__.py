@@ -8,6 +8,7 @@ extension cannot load on a GPU, the call raises.
 from .linear import linear, fold_rms_into_linear, EPI_BIAS, EPI_GELU, EPI_TANH, EPI_RESIDUAL, EPI_RELU  # noqa: F401
 from .linear import linear_ln, fold_ln_into_linear, fold_ok, ln_partials_ref, ln_finalize, row_parts_ref  # noqa: F401
 from .linear import LAYOUT_A, LAYOUT_C, LAYOUT_R, to_image_order, from_image_order, image_order_ok  # noqa: F401
+from .linear import LAYOUT_A_FRAG, LAYOUT_C_FRAG, LAYOUT_R_FRAG, to_fragment_order, from_fragment_order  # noqa: F401
 from .linear import row_totals_parts_ref, batch_invariant, set_batch_invariant  # noqa: F401
 from .linear_i8 import quantize_rows_i8, linear_i8, linear_i8_ok, quantize_rows_i8_ref, linear_i8_ref  # noqa: F401
 from .linear_i8 import layernorm_quant_i8  # noqa: F401

@@ -354,6 +354,8 @@ def linear_ln(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, act: Opti
     * ``part_out [N/256, M, 2]``: row partials of the output (fp32, before bf16 rounding).
     * ``layout`` (GPU only; ``LAYOUT_A | LAYOUT_C | LAYOUT_R``): ``x`` / the output / ``residual`` lie
       in K-tile image order (:func:`to_image_order`) instead of row-major; plain bias is allowed then.
+      ``LAYOUT_A_FRAG`` / ``LAYOUT_C_FRAG`` / ``LAYOUT_R_FRAG``: that operand in fragment order
+      (:func:`to_fragment_order`), for the combinations the folded BERT encoder runs.
     """
     in_norm, res_norm = in_fin is not None, res_fin is not None
     check(act in (None, "gelu"), f"linear_ln: activation {act!r} not supported")
@@ -446,3 +448,31 @@ def from_image_order(x: torch.Tensor) -> torch.Tensor:
     M, W = x.shape
     check(M % 256 == 0 and W % 64 == 0, "image order needs M % 256 == 0 and W % 64 == 0")
     return x.reshape(M // 256, W // 64, 256, 64).permute(0, 2, 1, 3).contiguous().view(M, W)
+
+
+# fragment order: the operand's image bit plus "16-byte units inside an image in fragment order"
+LAYOUT_A_FRAG, LAYOUT_C_FRAG, LAYOUT_R_FRAG = LAYOUT_A | 8, LAYOUT_C | 16, LAYOUT_R | 32
+# 8-column chunk of a 32-column k-half held by lane row G after the epilogue's v_permlane16_swap
+FRAG_CHUNK_OF_LANE_ROW = (0, 2, 1, 3)
+
+
+def to_fragment_order(x: torch.Tensor) -> torch.Tensor:
+    """Row-major ``[M, W]`` -> fragment order (same shape and storage size): image order's
+    ``[M/256][W/64]`` images of 256 rows x 64 columns, and inside an image ``[16 row groups of 16
+    rows][2 k-halves of 32 columns][64 units of 16 bytes]``, unit ``u`` holding row ``u % 16`` of the
+    group and the 8 columns of chunk ``(0, 2, 1, 3)[u // 16]`` of the half: what lane ``u`` of the
+    producing GEMM wave holds, and the LDS A image of the consuming one."""
+    M, W = x.shape
+    check(M % 256 == 0 and W % 64 == 0, "fragment order needs M % 256 == 0 and W % 64 == 0")
+    t = x.reshape(M // 256, 16, 16, W // 64, 2, 4, 8)  # image row, group, row, image column, half, chunk, column
+    t = t[:, :, :, :, :, list(FRAG_CHUNK_OF_LANE_ROW), :]
+    return t.permute(0, 3, 1, 4, 5, 2, 6).contiguous().view(M, W)
+
+
+def from_fragment_order(x: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`to_fragment_order`."""
+    M, W = x.shape
+    check(M % 256 == 0 and W % 64 == 0, "fragment order needs M % 256 == 0 and W % 64 == 0")
+    t = x.reshape(M // 256, W // 64, 16, 2, 4, 16, 8).permute(0, 2, 5, 1, 3, 4, 6)
+    t = t[:, :, :, :, :, list(FRAG_CHUNK_OF_LANE_ROW), :]  # the chunk permutation is its own inverse
+    return t.contiguous().view(M, W)

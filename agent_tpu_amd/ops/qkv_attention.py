@@ -53,7 +53,8 @@ def qkv_attention(x: torch.Tensor, w_h: torch.Tensor, b_h: torch.Tensor, lens: t
     (:func:`qkv_head_order`). ``in_fin [M, 2]`` + ``colsum_h``: ``x`` holds raw LayerNorm
     inputs and the weights are folded (:func:`ops.fold_ln_into_linear`), as ``linear_ln``.
     Keys ``>= lens[b]`` are masked. ``layout`` (GPU only): ``ops.LAYOUT_A`` / ``ops.LAYOUT_C``, ``x`` /
-    the context in K-tile image order (:func:`ops.to_image_order`)."""
+    the context in K-tile image order (:func:`ops.to_image_order`); ``ops.LAYOUT_A_FRAG | ops.LAYOUT_C``
+    (with ``in_fin``): ``x`` in fragment order (:func:`ops.to_fragment_order`)."""
     scale = 1.0 / math.sqrt(HEAD_DIM) if scale is None else float(scale)
     M, K = x.shape
     N = w_h.shape[0]
