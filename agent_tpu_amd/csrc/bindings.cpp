@@ -406,6 +406,18 @@ PYBIND11_MODULE(_atpu, m) {
                              Sq, P<const uint8_t>(table), header.data(), static_cast<size_t>(table_bytes),
                              max_row_bytes, S(stream), text_bytes);
         });
+  m.def("pair_assemble",
+        [](uintptr_t ids_q, uintptr_t lens_q, uintptr_t ids_p, uintptr_t lens_p, uintptr_t qidx, uintptr_t ids,
+           uintptr_t type_ids, uintptr_t lens, int rows, int Q, int Sq, int mq, int cls, int sep, int pad,
+           uintptr_t stream) {
+          pair_assemble(P<const int32_t>(ids_q), P<const int32_t>(lens_q), P<const int32_t>(ids_p),
+                        P<const int32_t>(lens_p), P<const int32_t>(qidx), P<int32_t>(ids), P<int32_t>(type_ids),
+                        P<int32_t>(lens), rows, Q, Sq, mq, cls, sep, pad, S(stream));
+        });
+  m.def("group_topk", [](uintptr_t scores, uintptr_t goff, uintptr_t idx, uintptr_t val, int rows, int Q, int k,
+                         uintptr_t stream) {
+    group_topk(P<const float>(scores), P<const int32_t>(goff), P<int32_t>(idx), P<float>(val), rows, Q, k, S(stream));
+  });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

@@ -309,6 +309,22 @@ void tokenize_wordpiece(const uint8_t* text, const int32_t* offsets, int32_t* id
                         const uint8_t* table, const int32_t* header, size_t table_bytes, int max_row_bytes,
                         hipStream_t stream, long long text_bytes);
 
+// ------------------------------------------------------ re-ranker (rerank.hip)
+// Pair rows "atpu-pair v1" (agent_tpu_amd/tokenizer.py pair_rows is the twin) from single-segment
+// rows as the tokenizers emit them: passage row r with query row q = clamp(qidx[r], 0, Q-1) becomes
+// [CLS] q_tok[0:nq] [SEP] p_tok[0:np] [SEP] [PAD]..., nq = min(lens_q[q]-2, mq, S-3),
+// np = min(lens_p[r]-2, S-3-nq) (lens clamped into [2, S]); type_ids 1 on the passage segment and
+// its [SEP]; lens = nq + np + 3. S >= 4, Q >= 1, mq >= 0; nothing outside the given rows is touched.
+void pair_assemble(const int32_t* ids_q, const int32_t* lens_q, const int32_t* ids_p, const int32_t* lens_p,
+                   const int32_t* qidx, int32_t* ids, int32_t* type_ids, int32_t* lens, int P, int Q, int S, int mq,
+                   int cls, int sep, int pad, hipStream_t stream);
+// Per-group top-k of scores [P]: group q is rows goff[q]..goff[q+1]-1 (goff [Q+1], clamped into
+// [0, P]); idx [Q, k] is the index within the group, val [Q, k] the score, ordered by (value desc,
+// index asc), +0.0 and -0.0 tie, a NaN ranks and is returned as -inf; a short group is padded
+// with (-inf, -1). k in [1, 32].
+void group_topk(const float* scores, const int32_t* goff, int32_t* idx, float* val, int P, int Q, int k,
+                hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

@@ -521,3 +521,12 @@ class BertClassifier:
         """Returns ``(logits[B,C] fp32, topk_idx[B,k] int32, topk_prob[B,k] fp32)``."""
         B, S = ids.shape
         return self.head(self.encoder(ids, lens, type_ids), B, S, k)
+
+    def score(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor],
+              label: int = 0) -> torch.Tensor:
+        """Cross-encoder relevance ``[B]`` fp32 of pair rows (``ops.pair_assemble``): the raw logit of
+        class ``label`` of :meth:`forward` (no softmax: a one-logit head's probability is always 1)."""
+        if not 0 <= int(label) < self.cfg.num_labels:
+            raise ValueError("label must be in [0, num_labels)")
+        logits, _, _ = self.forward(ids, lens, 1, type_ids=type_ids)
+        return logits[:, int(label)]

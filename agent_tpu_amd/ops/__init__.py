@@ -22,5 +22,6 @@ from .pool import pool_embed, pool_embed_ok, pool_embed_ref  # noqa: F401
 from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
+from .rerank import pair_assemble, pair_assemble_ref, group_topk, group_topk_ref  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

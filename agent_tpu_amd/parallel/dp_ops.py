@@ -15,8 +15,9 @@ fault, which drops that rank from the DP group (elastic shrink, SURVEY.md
 Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
 ``risk_accumulate`` (C3 all-reduce of {count,sum,min,max}),
 ``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
-tasks (C2 all-gather of embeddings) and ``map_search`` (C2 all-gather of
-per-rank top-k lists, merged on rank 0).
+tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
+per-rank top-k lists, merged on rank 0) and the ``map_rerank`` tasks (C2
+all-gather of pair scores, ranked on rank 0).
 """
 from __future__ import annotations
 
@@ -559,6 +560,39 @@ def search_batch_task(payload: Dict[str, Any]) -> Any:
 
     rank, ws = world()
     return ms.search_batch(payload["payloads"], rank, ws)
+
+
+# --------------------------------------------------------------- map_rerank
+@dp_task("map_rerank")
+def rerank_task(payload: Dict[str, Any]) -> Any:
+    """One map_rerank job: the pairs split contiguously over the ranks, each rank scoring its slice
+    with the queries it needs, the scores all-gathered (C2) after the error exchange and ranked on
+    rank 0 (:func:`ops.map_rerank.rerank_batch` with one job)."""
+    from ops import map_rerank as mr
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    res = mr.rerank_batch(h, [payload], rank, ws)
+    if rank != 0:
+        return None
+    kind, value = res[0]
+    if kind == "err":
+        raise value
+    return value
+
+
+@dp_task("map_rerank_batch")
+def rerank_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several map_rerank jobs of one lease (same model, max_query_tokens and label): one collective
+    model load, then :func:`ops.map_rerank.rerank_batch` on every rank."""
+    from ops import map_rerank as mr
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    payloads = payload["payloads"]
+    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    return mr.rerank_batch(h, payloads, rank, ws)
 
 
 # ---------------------------------------------------------- risk_accumulate

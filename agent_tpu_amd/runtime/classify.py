@@ -30,7 +30,8 @@ from .. import ops
 from .._native import native
 from ..models.bert import BertClassifier, BertConfig
 from ..models.params import ParamPack
-from ..tokenizer import DEFAULT_MAX_ROW_BYTES, WordPieceVocab, pack_rows
+from ..tokenizer import (CLS_ID, DEFAULT_MAX_ROW_BYTES, PAD_ID, SEP_ID, WordPieceVocab, default_max_query_tokens,
+                         pack_rows)
 from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
@@ -46,6 +47,15 @@ class BatchResult:
 class EmbedResult:
     rows: int
     emb: torch.Tensor    # [rows, H] fp32 (host)
+
+
+@dataclass
+class RerankResult:
+    queries: int
+    pairs: int
+    idx: torch.Tensor     # [queries, k] int32 (host): index within the query's passages, -1 past its end
+    score: torch.Tensor   # [queries, k] fp32 (host): the ranked scores (after ``activation``)
+    scores: torch.Tensor  # [pairs] fp32 (host): every pair's raw score, in input order
 
 
 @dataclass
@@ -371,6 +381,13 @@ class ClassifyEngine:
         tm = stats.timing_ms  # host_* spans (+ roctx ranges under MI355X_TRACE=1); device_* from hipEvents
         dst = DeviceStages() if stage_timing else None
         ev = DeviceStages.event
+        if dst and self.use_graph:
+            # capture the stage graphs of every slot this run replays before the first event: a lazy
+            # capture inside the loop is host time that device_span_ms would count as a pipeline gap
+            graphed = nb if ops.batch_invariant() else n // self.B  # batches that run the full-batch step
+            for slot in range(min(self.n_slots, graphed)):
+                with torch.cuda.stream(streams[slot]):
+                    self._staged_graphs(slot)
         with span("host_csv_stage_ms", tm):
             st.submit(0, table, start, min(self.B, n), col, self.max_row_bytes, host_threads)
         def stage_next(i: int) -> None:
@@ -578,6 +595,165 @@ class ClassifyEngine:
         stats.wall_s = time.perf_counter() - t0
         return out, stats
 
+    # ----------------------------------------------------------------- rerank
+    # Cross-encoder scoring of (query, passage) pairs on the bucket machinery of the small-job
+    # forms: per chunk of at most B pairs one H2D of the packed texts, one graph (tokenize the
+    # chunk's queries, tokenize its passages, pair_assemble, model.score) and one D2D of the
+    # scores; after the last chunk one group_topk launch and one D2H.
+    def _special_ids(self) -> Tuple[int, int, int]:
+        if self.vocab is not None:
+            return self.vocab.cls_id, self.vocab.sep_id, self.vocab.pad_id
+        return CLS_ID, SEP_ID, PAD_ID
+
+    def _rerank_bufs(self) -> Dict[str, torch.Tensor]:
+        """The re-ranker's extra buffers, allocated on first use: a text / offsets slot and token rows
+        for the queries, the pair rows with their type ids, and the rows' query index."""
+        if getattr(self, "_rr", None) is None:
+            dev, B, S = self.device, self.B, self.S
+
+            def i32(*shape, **kw):
+                return torch.zeros(shape, dtype=torch.int32, **kw)
+
+            rr = {"text_q": torch.empty(B * self.max_row_bytes, dtype=torch.uint8, device=dev),
+                  "offs_q": i32(B + 1, device=dev), "ids_q": i32(B, S, device=dev), "lens_q": i32(B, device=dev),
+                  "ids": i32(B, S, device=dev), "type_ids": i32(B, S, device=dev), "lens": i32(B, device=dev),
+                  "qidx": i32(B, device=dev)}
+            if dev.type == "cuda":
+                rr.update(pin_text_q=torch.zeros(B * self.max_row_bytes, dtype=torch.uint8, pin_memory=True),
+                          pin_offs_q=i32(B + 1, pin_memory=True), pin_qidx=i32(B, pin_memory=True))
+            self._rr = rr
+        return self._rr
+
+    def _rerank_step(self, bucket: int, mq: int, label: int) -> torch.Tensor:
+        """Raw scores ``[bucket]`` of the pairs staged in slot 0 (passages) and the query slot."""
+        r = self._rerank_bufs()
+        cls_id, sep_id, pad_id = self._special_ids()
+        self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
+        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+        ops.pair_assemble(r["ids_q"][:bucket], r["lens_q"][:bucket], self.ids_s[0], self.lens_s[0], r["qidx"], mq,
+                          cls_id, sep_id, pad_id, ids=r["ids"], type_ids=r["type_ids"], lens=r["lens"], rows=bucket)
+        return self.model.score(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], label)
+
+    def _rerank_bucket(self, bucket: int, mq: int, label: int) -> torch.Tensor:
+        if not self.use_graph:
+            return self._rerank_step(bucket, mq, label)
+        gk = ("rerank", bucket, mq, label)
+        if gk not in self._bgraphs:
+            # the WordPiece table is on the device since __init__; the warm-up run loads the code objects
+            self._warm(lambda: self._rerank_step(bucket, mq, label))
+            self._bgraphs[gk] = capture_graph(lambda: self._rerank_step(bucket, mq, label), pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def _encode_rows(self, rows: Sequence) -> List[bytes]:
+        return [(r if isinstance(r, (bytes, bytearray)) else r.encode("utf-8"))[:self.max_row_bytes] for r in rows]
+
+    @staticmethod
+    def _check_goff(goff: Sequence[int], Q: int, P: int) -> List[int]:
+        goff = [int(g) for g in goff]
+        if len(goff) != Q + 1 or goff[0] != 0 or goff[-1] != P or any(a > b for a, b in zip(goff, goff[1:])):
+            raise ValueError("goff must be Q + 1 non-decreasing offsets from 0 to len(passages)")
+        return goff
+
+    def score_pairs(self, queries: Sequence, passages: Sequence, goff: Sequence[int],
+                    max_query_tokens: Optional[int] = None, label: int = 0) -> torch.Tensor:
+        """Raw cross-encoder scores ``[P]`` fp32, left on the engine's device (a DP caller all-gathers
+        them): ``passages`` is the flat list of all candidates, query ``q`` owning rows
+        ``goff[q] .. goff[q + 1] - 1``; the score of a pair is the logit of class ``label`` of the row
+        ``[CLS] query [SEP] passage [SEP]`` (``ops.pair_assemble``, the query cut at
+        ``max_query_tokens``, default ``min(32, (S - 3) // 2)``)."""
+        Q, P = len(queries), len(passages)
+        goff = self._check_goff(goff, Q, P)
+        if self.S < 4:
+            raise ValueError("rerank_pairs needs seq_len >= 4")
+        mq = default_max_query_tokens(self.S) if max_query_tokens is None else max_query_tokens
+        if isinstance(mq, bool) or not isinstance(mq, int) or mq < 0:
+            raise ValueError("max_query_tokens must be an int >= 0")
+        if isinstance(label, bool) or not isinstance(label, int) or not 0 <= label < self.cfg.num_labels:
+            raise ValueError("label must be in [0, num_labels)")
+        dev, cuda = self.device, self.device.type == "cuda"
+        scores = torch.empty(P, dtype=torch.float32, device=dev)
+        if P == 0:
+            return scores
+        qid = np.repeat(np.arange(Q, dtype=np.int64), np.diff(np.asarray(goff, dtype=np.int64)))  # row -> query
+        r = self._rerank_bufs()
+        pin = self._pinned() if cuda else None
+        free = None  # the event after which the pinned rows of the previous chunk may be overwritten
+        for c0 in range(0, P, self.B):
+            m = min(self.B, P - c0)
+            used, local = np.unique(qid[c0:c0 + m], return_inverse=True)  # the chunk's queries: at most m
+            text_p, offs_p = pack_rows(self._encode_rows(passages[c0:c0 + m]))
+            text_q, offs_q = pack_rows(self._encode_rows([queries[int(q)] for q in used]))
+            local = local.astype(np.int32)
+            if not cuda:
+                ids_q, lens_q = self._tokenize(torch.from_numpy(text_q), torch.from_numpy(offs_q))
+                ids_p, lens_p = self._tokenize(torch.from_numpy(text_p), torch.from_numpy(offs_p))
+                ids, types, lens = ops.pair_assemble(ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local), mq,
+                                                     *self._special_ids())
+                scores[c0:c0 + m] = self.model.score(ids, lens, types, label)
+                continue
+            bk, nq = self._bucket(m), len(used)
+            if free is not None:
+                free.synchronize()
+            pin["text"][:text_p.size].copy_(torch.from_numpy(text_p))
+            pin["offs"][:m + 1].copy_(torch.from_numpy(offs_p))
+            pin["offs"][m + 1:bk + 1].fill_(int(offs_p[-1]))  # padding rows: an empty passage ...
+            r["pin_text_q"][:text_q.size].copy_(torch.from_numpy(text_q))
+            r["pin_offs_q"][:nq + 1].copy_(torch.from_numpy(offs_q))
+            r["pin_offs_q"][nq + 1:bk + 1].fill_(int(offs_q[-1]))
+            r["pin_qidx"][:m].copy_(torch.from_numpy(local))
+            r["pin_qidx"][m:bk].zero_()  # ... of query 0, their scores dropped
+            if text_p.size:
+                self.text[0][:text_p.size].copy_(pin["text"][:text_p.size], non_blocking=True)
+            self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
+            if text_q.size:
+                r["text_q"][:text_q.size].copy_(r["pin_text_q"][:text_q.size], non_blocking=True)
+            r["offs_q"][:bk + 1].copy_(r["pin_offs_q"][:bk + 1], non_blocking=True)
+            r["qidx"][:bk].copy_(r["pin_qidx"][:bk], non_blocking=True)
+            free = torch.cuda.Event()
+            free.record()
+            scores[c0:c0 + m].copy_(self._rerank_bucket(bk, mq, label)[:m])
+        if free is not None:
+            free.synchronize()  # the pinned rows are free for the next call, whichever form it is
+        return scores
+
+    def rank_scores(self, scores: torch.Tensor, goff: Sequence[int], top_k: int = 10,
+                    activation: str = "none") -> RerankResult:
+        """The top ``top_k`` (1..32) of every query's own scores, in the total order (score descending,
+        index ascending) of ``ops.group_topk``: one launch and one D2H, which also brings every raw
+        score to the host. ``activation="sigmoid"`` maps the returned top-k values on the host, in
+        fp32, after the ranking on raw logits (monotone: the order is the same)."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        if activation not in ("none", "sigmoid"):
+            raise ValueError("activation must be 'none' or 'sigmoid'")
+        k, P = top_k, int(scores.numel())
+        Q = len(goff) - 1
+        goff = self._check_goff(goff, Q, P)
+        if P == 0 or Q == 0:
+            return RerankResult(Q, P, torch.full((Q, k), -1, dtype=torch.int32),
+                                torch.full((Q, k), float("-inf")), scores.cpu())
+        idx, val = ops.group_topk(scores, torch.tensor(goff, dtype=torch.int32).to(scores.device), k)
+        both = torch.cat([idx.view(torch.float32).reshape(-1), val.reshape(-1), scores]).cpu()  # one D2H, one sync
+        idx_h = both[:Q * k].clone().view(torch.int32).view(Q, k)
+        val_h = both[Q * k:2 * Q * k].clone().view(Q, k)
+        if activation == "sigmoid":
+            val_h = torch.where(idx_h >= 0, torch.sigmoid(val_h), val_h)
+        return RerankResult(Q, P, idx_h, val_h, both[2 * Q * k:].clone())
+
+    def rerank_pairs(self, queries: Sequence, passages: Sequence, goff: Sequence[int], top_k: int = 10,
+                     max_query_tokens: Optional[int] = None, label: int = 0,
+                     activation: str = "none") -> RerankResult:
+        """:meth:`score_pairs`, then :meth:`rank_scores`: every (query, passage) pair scored by the model
+        as a cross-encoder, each query's own passages ranked."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        if activation not in ("none", "sigmoid"):
+            raise ValueError("activation must be 'none' or 'sigmoid'")
+        scores = self.score_pairs(queries, passages, goff, max_query_tokens, label)
+        return self.rank_scores(scores, goff, top_k, activation)
+
     def memory_bytes(self) -> int:
         """Resident device bytes: weights, the LayerNorm-folded weight copies once built
         (they are ~45 % of the encoder weights), staging and token buffers."""
@@ -590,6 +766,8 @@ class ClassifyEngine:
         egraphs = list(self._egraphs.values()) + [v for k, v in (getattr(self, "_bgraphs", None) or {}).items()
                                                   if k[0] == "embed"]
         extra += sum(o.numel() * o.element_size() for _, o in egraphs)
+        # rerank: its query slot, pair rows and type ids (nothing until the first rerank call)
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_rr", None) or {}).values() if t.is_cuda)
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

@@ -47,6 +47,11 @@ separate instead of being deleted; a literal special-token string in the text
 (``[SEP]``) is punctuation plus a word. On rows of printable ASCII plus
 ``\\t \\n \\r`` without special-token strings the output equals
 ``BertTokenizer(vocab_file, do_lower_case=True)`` exactly (tested).
+
+atpu-pair v1 — cross-encoder rows ``[CLS] query [SEP] passage [SEP]`` with their
+``token_type_ids``, assembled from the single-segment rows of either tokenizer
+(:func:`pair_rows`; HIP kernel ``csrc/kernels/rerank.hip``, bit-for-bit). The spec is
+the docstring of :func:`pair_rows`.
 """
 from __future__ import annotations
 
@@ -271,3 +276,57 @@ class WordPieceVocab:
             t = torch.from_numpy(self.table).to(device)
             self._device[key] = t
         return t
+
+
+# ------------------------------------------------------------------ atpu-pair v1
+def default_max_query_tokens(seq_len: int) -> int:
+    """The query budget of a pair row when the caller names none: ``min(32, (S - 3) // 2)``."""
+    return min(32, (int(seq_len) - 3) // 2)
+
+
+def pair_rows(ids_q: np.ndarray, lens_q: np.ndarray, ids_p: np.ndarray, lens_p: np.ndarray, qidx: np.ndarray,
+              max_query_tokens: int, cls_id: int = CLS_ID, sep_id: int = SEP_ID,
+              pad_id: int = PAD_ID) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """atpu-pair v1: cross-encoder rows ``[CLS] query [SEP] passage [SEP]`` assembled from the
+    single-segment rows either tokenizer emits (``[CLS] t... [SEP] [PAD]...``, ``len = n + 2``);
+    pure-Python twin of ``csrc/kernels/rerank.hip`` ``pair_assemble_kernel``, bit-for-bit.
+
+    For passage row ``r`` with ``q = clamp(qidx[r], 0, Q - 1)``, ``S`` the row width (>= 4):
+
+    * ``nq = min(clamp(lens_q[q], 2, S) - 2, max_query_tokens, S - 3)``;
+    * ``np = min(clamp(lens_p[r], 2, S) - 2, S - 3 - nq)``;
+    * ``ids = [CLS] q_tok[0:nq] [SEP] p_tok[0:np] [SEP]`` then ``[PAD]``;
+    * ``type_ids`` 0 on the first ``nq + 2`` positions, 1 on the next ``np + 1``, 0 on padding;
+    * ``len = nq + np + 3``.
+
+    Where ``max_query_tokens`` does not cut the query this is HF ``BertTokenizer(q, p,
+    truncation="only_second", max_length=S, padding="max_length")`` (``input_ids``,
+    ``token_type_ids``, attention length), under the caveats of atpu-wordpiece v1.
+    Returns ``(ids[P, S], type_ids[P, S], lens[P])``, all int32."""
+    ids_q, ids_p = np.asarray(ids_q, dtype=np.int32), np.asarray(ids_p, dtype=np.int32)
+    lens_q, lens_p = np.asarray(lens_q, dtype=np.int32), np.asarray(lens_p, dtype=np.int32)
+    qidx = np.asarray(qidx, dtype=np.int32)
+    if ids_q.ndim != 2 or ids_p.ndim != 2 or ids_q.shape[1] != ids_p.shape[1]:
+        raise ValueError("pair_rows: ids_q [Q, S] and ids_p [P, S]")
+    Q, S = ids_q.shape
+    P = ids_p.shape[0]
+    mq = int(max_query_tokens)
+    if S < 4 or Q < 1 or mq < 0:
+        raise ValueError("pair_rows: S >= 4, Q >= 1 and max_query_tokens >= 0")
+    if lens_q.shape != (Q,) or lens_p.shape != (P,) or qidx.shape != (P,):
+        raise ValueError("pair_rows: lens_q [Q], lens_p [P] and qidx [P]")
+    ids = np.full((P, S), pad_id, dtype=np.int32)
+    types = np.zeros((P, S), dtype=np.int32)
+    lens = np.zeros(P, dtype=np.int32)
+    for r in range(P):
+        q = min(max(int(qidx[r]), 0), Q - 1)
+        nq = min(min(max(int(lens_q[q]), 2), S) - 2, mq, S - 3)
+        n_p = min(min(max(int(lens_p[r]), 2), S) - 2, S - 3 - nq)
+        ids[r, 0] = cls_id
+        ids[r, 1:1 + nq] = ids_q[q, 1:1 + nq]
+        ids[r, 1 + nq] = sep_id
+        ids[r, 2 + nq:2 + nq + n_p] = ids_p[r, 1:1 + n_p]
+        ids[r, 2 + nq + n_p] = sep_id
+        types[r, 2 + nq:3 + nq + n_p] = 1
+        lens[r] = nq + n_p + 3
+    return ids, types, lens
