@@ -418,6 +418,14 @@ PYBIND11_MODULE(_atpu, m) {
                          uintptr_t stream) {
     group_topk(P<const float>(scores), P<const int32_t>(goff), P<int32_t>(idx), P<float>(val), rows, Q, k, S(stream));
   });
+  m.def("span_topk",
+        [](uintptr_t x, uintptr_t fin, uintptr_t u, uintptr_t su, uintptr_t c, uintptr_t type_ids, uintptr_t lens,
+           uintptr_t span, uintptr_t score, uintptr_t null, uintptr_t logits, int B, int Sq, int H, int max_len, int n,
+           uintptr_t stream) {
+          span_topk(P<const bf16>(x), P<const float>(fin), P<const float>(u), P<const float>(su), P<const float>(c),
+                    P<const int32_t>(type_ids), P<const int32_t>(lens), P<int32_t>(span), P<float>(score),
+                    P<float>(null), P<float>(logits), B, Sq, H, max_len, n, S(stream));
+        });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

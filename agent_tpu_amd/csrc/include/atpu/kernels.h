@@ -325,6 +325,20 @@ void pair_assemble(const int32_t* ids_q, const int32_t* lens_q, const int32_t* i
 void group_topk(const float* scores, const int32_t* goff, int32_t* idx, float* val, int P, int Q, int k,
                 hipStream_t stream);
 
+// ------------------------------------------- question answering (span_head.hip)
+// Start / end logits of the pair rows x [B*S, H] and the n best answer spans of each row's passage.
+// With fin [B*S, 2] = (rstd, rstd*mu) the rows are raw and the LayerNorm is folded into the head:
+// logit_c[j] = rstd_j (x_j . u_c) - (rstd_j mu_j) su_c + c_c; without it logit_c[j] = x_j . u_c + c_c.
+// u [2, H], su [2], c [2] fp32. len = clamp(lens[b], 2, S); positions >= len have logit -inf.
+// Candidates (i, j): lo <= i <= j <= hi, j - i < max_len, lo = the first position of type 1, hi =
+// len - 2; value logit_0[i] + logit_1[j] (a NaN ranks as -inf), order (value desc, i * S + j asc).
+// span [B, n, 2] passage-relative (i - lo, j - lo), score [B, n]; exhausted slots (-1, -1), -inf.
+// null [B] = logit_0[0] + logit_1[0]; logits [B, S, 2] optional (null: not written).
+// 4 <= S <= 512, H % 64 == 0 in [64, 1024], n in [1, 32], max_len in [1, S]; B == 0: no launch.
+void span_topk(const bf16* x, const float* fin, const float* u, const float* su, const float* c,
+               const int32_t* type_ids, const int32_t* lens, int32_t* span, float* score, float* null, float* logits,
+               int B, int S, int H, int max_len, int n, hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

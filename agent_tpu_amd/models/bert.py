@@ -40,6 +40,7 @@ class BertConfig:
     type_vocab: int = 2
     num_labels: int = 2
     eps: float = 1e-12
+    qa_head: bool = False  # a span head (HF BertForQuestionAnswering qa_outputs) after the classifier
 
     @property
     def head_dim(self) -> int:
@@ -50,6 +51,8 @@ class BertConfig:
         emb = (self.vocab_size + self.max_positions + self.type_vocab) * H + 2 * H
         layer = 4 * H * H + 4 * H + 2 * H * I + I + H + 4 * H
         head = H * H + H + self.num_labels * H + self.num_labels
+        if self.qa_head:
+            head += 2 * H + 2
         return emb + L * layer + head
 
     def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True,
@@ -121,6 +124,9 @@ def param_specs(cfg: BertConfig):
     yield "pool_b", (H,), f32
     yield "cls_w", (C, H), bf
     yield "cls_b", (C,), f32
+    if cfg.qa_head:
+        yield "qa_w", (2, H), bf
+        yield "qa_b", (2,), f32
 
 
 def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: float = 0.0,
@@ -148,8 +154,9 @@ def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: flo
 
 
 def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPack:
-    """Build a pack from a transformers ``BertForSequenceClassification`` state dict, or from a
-    plain ``BertModel`` one (no ``bert.`` prefix, no classifier, the pooler optional): head
+    """Build a pack from a transformers ``BertForSequenceClassification`` state dict, from a
+    ``BertForQuestionAnswering`` one (``qa_outputs``; no pooler, no classifier; ``cfg.qa_head``), or from
+    a plain ``BertModel`` one (no ``bert.`` prefix, no classifier, the pooler optional): head
     tensors the dict does not have stay zero."""
     pack = ParamPack(param_specs(cfg))
     if "embeddings.word_embeddings.weight" in sd and "bert.embeddings.word_embeddings.weight" not in sd:
@@ -179,8 +186,9 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPac
         put(f"l{i}.ln2_g", sd[b + "output.LayerNorm.weight"])
         put(f"l{i}.ln2_b", sd[b + "output.LayerNorm.bias"])
     for name, key in (("pool_w", "bert.pooler.dense.weight"), ("pool_b", "bert.pooler.dense.bias"),
-                      ("cls_w", "classifier.weight"), ("cls_b", "classifier.bias")):
-        if key in sd:
+                      ("cls_w", "classifier.weight"), ("cls_b", "classifier.bias"),
+                      ("qa_w", "qa_outputs.weight"), ("qa_b", "qa_outputs.bias")):
+        if key in sd and name in pack:
             put(name, sd[key])
     return pack
 
@@ -247,6 +255,11 @@ class BertClassifier:
         # vector by pool_embed (ops/pool.py); ATPU_EMBED_FUSED=0 finishes every row with
         # ops.layernorm and pools the normalised rows
         self.embed_fused = os.getenv("ATPU_EMBED_FUSED", "1") not in ("0", "false", "no")
+        # answer spans on the folded encoder: the last LayerNorm folded into the span head by
+        # span_topk (ops/span.py); ATPU_ANSWER_FUSED=0 finishes every row with ops.layernorm and
+        # runs the same kernel on the normalised rows
+        self.answer_fused = os.getenv("ATPU_ANSWER_FUSED", "1") not in ("0", "false", "no")
+        self._span_inputs: Optional[Dict[str, torch.Tensor]] = None
 
     # ------------------------------------------------------------ LN folding
     def folded(self) -> Dict[str, torch.Tensor]:
@@ -510,6 +523,44 @@ class BertClassifier:
                                   normalize=normalize)
         h = self.encode(ids, lens, type_ids, cls_only_last=False)
         return ops.pool_embed(h, lens, B, normalize=normalize)
+
+    # ------------------------------------------------------------ question answering
+    def span_inputs(self) -> Dict[str, torch.Tensor]:
+        """The span head as ``ops.span_topk`` takes it (fp32, built once, on the device). Fused with the
+        last layer's LayerNorm: ``u [2, H] = ln2_g * qa_w``, ``su [2]`` = the row sums of ``u`` and
+        ``c [2] = ln2_b . qa_w + qa_b``, both accumulated in fp64 and rounded once. Unfused: ``w`` =
+        ``qa_w`` as fp32, ``z`` = zeros, ``b`` = ``qa_b``."""
+        if not self.cfg.qa_head:
+            raise ValueError("model has no QA head")
+        if self._span_inputs is None:
+            p = self.p
+            ln2 = f"l{self.cfg.layers - 1}."
+            w = p["qa_w"].float().contiguous()
+            b = p["qa_b"].float().contiguous()
+            u = (p[ln2 + "ln2_g"].float().view(1, -1) * w).contiguous()
+            su = u.double().sum(1).float().contiguous()
+            c = ((p[ln2 + "ln2_b"].double().view(1, -1) * w.double()).sum(1) + b.double()).float().contiguous()
+            self._span_inputs = {"u": u, "su": su, "c": c, "w": w, "z": torch.zeros_like(b), "b": b}
+        return self._span_inputs
+
+    def spans(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, max_answer_tokens: int,
+              n_best: int, logits_out: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Answer spans of pair rows (``ops.pair_assemble``): ``(span [B, n_best, 2] int32 passage-relative
+        token spans, score [B, n_best] fp32, null [B] fp32)`` of :func:`ops.span_topk`; ``logits_out
+        [B, S, 2]`` fp32, when given, receives the start / end logits.
+
+        Every layer runs in full. On the folded encoder the final LayerNorm is not run over the rows
+        but folded into the span head (``span_topk`` with ``fin``)."""
+        B, S = ids.shape
+        si = self.span_inputs()
+        if ids.is_cuda and self.answer_fused and self.can_fold(B, S):
+            g, fin, _ = self.encode_folded(ids, lens, type_ids, raw=True)
+            return ops.span_topk(g, lens, type_ids, B, si["u"], si["su"], si["c"], max_answer_tokens, n_best,
+                                 fin=fin, logits_out=logits_out)
+        h = self.encode(ids, lens, type_ids, cls_only_last=False)
+        return ops.span_topk(h, lens, type_ids, B, si["w"], si["z"], si["b"], max_answer_tokens, n_best,
+                             logits_out=logits_out)
 
     def head(self, h: torch.Tensor, B: int, S: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Pooler + classifier + softmax/top-k (K7) over encoder states ``h``."""

@@ -23,5 +23,6 @@ from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .rerank import pair_assemble, pair_assemble_ref, group_topk, group_topk_ref  # noqa: F401
+from .span import span_topk, span_topk_ok, span_topk_ref, span_logits_ref, span_select_ref  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

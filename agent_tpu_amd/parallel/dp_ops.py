@@ -595,6 +595,39 @@ def rerank_batch_task(payload: Dict[str, Any]) -> Any:
     return mr.rerank_batch(h, payloads, rank, ws)
 
 
+# --------------------------------------------------------------- map_answer
+@dp_task("map_answer")
+def answer_task(payload: Dict[str, Any]) -> Any:
+    """One map_answer job: the (question, passage) pairs split contiguously over the ranks, each rank
+    reading its slice, the per-pair span / score / null rows all-gathered (C2) after the error exchange
+    and ranked on rank 0 (:func:`ops.map_answer.answer_batch` with one job)."""
+    from ops import map_answer as ma
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    res = ma.answer_batch(h, [payload], rank, ws)
+    if rank != 0:
+        return None
+    kind, value = res[0]
+    if kind == "err":
+        raise value
+    return value
+
+
+@dp_task("map_answer_batch")
+def answer_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several map_answer jobs of one lease (same model, max_query_tokens and max_answer_tokens): one
+    collective model load, then :func:`ops.map_answer.answer_batch` on every rank."""
+    from ops import map_answer as ma
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    payloads = payload["payloads"]
+    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    return ma.answer_batch(h, payloads, rank, ws)
+
+
 # ---------------------------------------------------------- risk_accumulate
 def _local_values(payload: Dict[str, Any], rank: int, ws: int) -> Tuple[torch.Tensor, int]:
     """This rank's slice of a ``values`` / ``items`` payload, as fp64 (CSV payloads stream

@@ -31,7 +31,7 @@ from .._native import native
 from ..models.bert import BertClassifier, BertConfig
 from ..models.params import ParamPack
 from ..tokenizer import (CLS_ID, DEFAULT_MAX_ROW_BYTES, PAD_ID, SEP_ID, WordPieceVocab, default_max_query_tokens,
-                         pack_rows)
+                         pack_rows, token_spans)
 from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
@@ -56,6 +56,19 @@ class RerankResult:
     idx: torch.Tensor     # [queries, k] int32 (host): index within the query's passages, -1 past its end
     score: torch.Tensor   # [queries, k] fp32 (host): the ranked scores (after ``activation``)
     scores: torch.Tensor  # [pairs] fp32 (host): every pair's raw score, in input order
+
+
+@dataclass
+class AnswerResult:
+    questions: int
+    pairs: int
+    # per question, best first: {"passage": index within the question's passages, "start" / "end": character
+    # offsets into that passage, "text", "score": the span's logit sum, "null_score": its pair's no-answer
+    # score, "tokens": the passage-relative token span}
+    answers: List[List[Dict[str, object]]]
+    span: torch.Tensor   # [pairs, n, 2] int32 (host): every pair's n best token spans, (-1, -1) past the last
+    score: torch.Tensor  # [pairs, n] fp32 (host)
+    null: torch.Tensor   # [pairs] fp32 (host)
 
 
 @dataclass
@@ -672,10 +685,26 @@ class ClassifyEngine:
             raise ValueError("max_query_tokens must be an int >= 0")
         if isinstance(label, bool) or not isinstance(label, int) or not 0 <= label < self.cfg.num_labels:
             raise ValueError("label must be in [0, num_labels)")
-        dev, cuda = self.device, self.device.type == "cuda"
-        scores = torch.empty(P, dtype=torch.float32, device=dev)
+        scores = torch.empty(P, dtype=torch.float32, device=self.device)
+        for c0, m, bk, rows in self._pair_chunks(queries, passages, goff, mq):
+            if rows is not None:
+                ids, types, lens = rows
+                scores[c0:c0 + m] = self.model.score(ids, lens, types, label)
+            else:
+                scores[c0:c0 + m].copy_(self._rerank_bucket(bk, mq, label)[:m])
+        return scores
+
+    def _pair_chunks(self, queries: Sequence, passages: Sequence, goff: List[int], mq: int):
+        """The chunk staging of the pair jobs (:meth:`score_pairs`, :meth:`span_pairs`): yields
+        ``(c0, m, bucket, rows)`` per chunk of at most ``B`` pairs. On the GPU the chunk's packed texts,
+        offsets (padding rows: empty passages of query 0) and query indices are copied through the
+        pinned rows into slot 0 and the query slot, ``rows`` is None and the caller runs its step on
+        ``bucket`` rows; on the CPU ``rows`` is the assembled ``(ids, type_ids, lens)``. Before a
+        chunk's pinned rows are overwritten the copies of the previous one have completed (``free``)."""
+        Q, P = len(queries), len(passages)
+        cuda = self.device.type == "cuda"
         if P == 0:
-            return scores
+            return
         qid = np.repeat(np.arange(Q, dtype=np.int64), np.diff(np.asarray(goff, dtype=np.int64)))  # row -> query
         r = self._rerank_bufs()
         pin = self._pinned() if cuda else None
@@ -689,9 +718,8 @@ class ClassifyEngine:
             if not cuda:
                 ids_q, lens_q = self._tokenize(torch.from_numpy(text_q), torch.from_numpy(offs_q))
                 ids_p, lens_p = self._tokenize(torch.from_numpy(text_p), torch.from_numpy(offs_p))
-                ids, types, lens = ops.pair_assemble(ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local), mq,
+                yield c0, m, None, ops.pair_assemble(ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local), mq,
                                                      *self._special_ids())
-                scores[c0:c0 + m] = self.model.score(ids, lens, types, label)
                 continue
             bk, nq = self._bucket(m), len(used)
             if free is not None:
@@ -713,10 +741,147 @@ class ClassifyEngine:
             r["qidx"][:bk].copy_(r["pin_qidx"][:bk], non_blocking=True)
             free = torch.cuda.Event()
             free.record()
-            scores[c0:c0 + m].copy_(self._rerank_bucket(bk, mq, label)[:m])
+            yield c0, m, bk, None
         if free is not None:
             free.synchronize()  # the pinned rows are free for the next call, whichever form it is
-        return scores
+
+    # ----------------------------------------------------------------- answer
+    # Extractive question answering on the pair rows of the re-ranker: per chunk one graph (tokenize
+    # the chunk's questions, tokenize its passages, pair_assemble, model.spans) and D2D copies of the
+    # spans into [P, n] buffers; after the last chunk one group_topk launch over the flattened
+    # [P * n] scores and one D2H. The host maps the returned token spans to character offsets.
+    def _answer_step(self, bucket: int, mq: int, max_len: int, n: int):
+        r = self._rerank_bufs()
+        cls_id, sep_id, pad_id = self._special_ids()
+        self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
+        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+        ops.pair_assemble(r["ids_q"][:bucket], r["lens_q"][:bucket], self.ids_s[0], self.lens_s[0], r["qidx"], mq,
+                          cls_id, sep_id, pad_id, ids=r["ids"], type_ids=r["type_ids"], lens=r["lens"], rows=bucket)
+        return self.model.spans(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], max_len, n)
+
+    def _answer_bucket(self, bucket: int, mq: int, max_len: int, n: int):
+        if not self.use_graph:
+            return self._answer_step(bucket, mq, max_len, n)
+        gk = ("answer", bucket, mq, max_len, n)
+        if gk not in self._bgraphs:
+            self.model.span_inputs()  # built here, not inside the capture
+            self._warm(lambda: self._answer_step(bucket, mq, max_len, n))
+            self._bgraphs[gk] = capture_graph(lambda: self._answer_step(bucket, mq, max_len, n), pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def _check_answer_args(self, top_k, max_answer_tokens, max_query_tokens) -> Tuple[int, int, int]:
+        if self.S < 4:
+            raise ValueError("answer_pairs needs seq_len >= 4")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.span.MAX_N:
+            raise ValueError("top_k must be an int in [1, 32]")
+        ma = max_answer_tokens
+        if isinstance(ma, bool) or not isinstance(ma, int) or not 1 <= ma <= self.S - 3:
+            raise ValueError("max_answer_tokens must be an int in [1, seq_len - 3]")
+        mq = default_max_query_tokens(self.S) if max_query_tokens is None else max_query_tokens
+        if isinstance(mq, bool) or not isinstance(mq, int) or mq < 0:
+            raise ValueError("max_query_tokens must be an int >= 0")
+        return top_k, ma, mq
+
+    def span_pairs(self, questions: Sequence, passages: Sequence, goff: Sequence[int], n_best: int = 3,
+                   max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The ``n_best`` answer spans of every (question, passage) pair: ``(span [P, n, 2] int32
+        passage-relative token spans, score [P, n] fp32, null [P] fp32)`` of ``ops.span_topk``, left on the
+        engine's device (a DP caller all-gathers them): views of the engine's ``[P, n]`` buffers, valid until
+        the next call. The pair layout is that of :meth:`score_pairs`."""
+        Q, P = len(questions), len(passages)
+        goff = self._check_goff(goff, Q, P)
+        n, ma, mq = self._check_answer_args(n_best, max_answer_tokens, max_query_tokens)
+        dev = self.device
+        if getattr(self, "_an", None) is None or self._an[0].shape[0] < P or self._an[0].shape[1] != n:
+            rows = max(P, self.B)  # one allocation serves every job of up to B pairs
+            self._an = (torch.empty((rows, n, 2), dtype=torch.int32, device=dev),
+                        torch.empty((rows, n), dtype=torch.float32, device=dev),
+                        torch.empty((rows,), dtype=torch.float32, device=dev))
+        span, score, null = (t[:P] for t in self._an)
+        for c0, m, bk, rows in self._pair_chunks(questions, passages, goff, mq):
+            if rows is not None:
+                ids, types, lens = rows
+                sp, sc, nl = self.model.spans(ids, lens, types, ma, n)
+            else:
+                sp, sc, nl = self._answer_bucket(bk, mq, ma, n)
+            span[c0:c0 + m].copy_(sp[:m]), score[c0:c0 + m].copy_(sc[:m]), null[c0:c0 + m].copy_(nl[:m])
+        return span, score, null
+
+    @staticmethod
+    def _char_span(full: bytes, a: int, b: int) -> Tuple[int, int, str]:
+        """The byte range ``[a, b)`` of ``full`` widened outward to UTF-8 character boundaries, as
+        ``(start, end, text)`` in characters of the decoded string."""
+        while a > 0 and 0x80 <= full[a] <= 0xBF:
+            a -= 1
+        while b < len(full) and 0x80 <= full[b] <= 0xBF:
+            b += 1
+        start = len(full[:a].decode("utf-8", "replace"))
+        text = full[a:b].decode("utf-8", "replace")
+        return start, start + len(text), text
+
+    def rank_spans(self, span: torch.Tensor, score: torch.Tensor, null: torch.Tensor, passages: Sequence,
+                   goff: Sequence[int], top_k: int = 3) -> "AnswerResult":
+        """Every question's ``top_k`` best spans over all of its pairs: one ``ops.group_topk`` launch over the
+        flattened ``[P * n]`` scores (offsets ``goff * n``; score descending, then pair and slot ascending)
+        and one D2H; the token spans of the returned answers are mapped to character offsets of their
+        passage on the host (``token_spans``, the row cut at ``max_row_bytes`` as the device cut it).
+        ``-inf`` entries are dropped."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        P, n = int(score.shape[0]), int(score.shape[1])
+        Q = len(goff) - 1
+        goff = self._check_goff(goff, Q, P)
+        if len(passages) != P:
+            raise ValueError("rank_spans: one passage per span row")
+        k = top_k
+        if P == 0 or Q == 0:
+            return AnswerResult(Q, P, [[] for _ in range(Q)], span.cpu(), score.cpu(), null.cpu())
+        idx, val = ops.group_topk(score.reshape(-1), torch.tensor([g * n for g in goff], dtype=torch.int32)
+                                  .to(score.device), k)
+        both = torch.cat([idx.view(torch.float32).reshape(-1), val.reshape(-1), span.view(torch.float32).reshape(-1),
+                          score.reshape(-1), null]).cpu()  # one D2H, one sync
+        cut = np.cumsum([0, Q * k, Q * k, P * n * 2, P * n, P]).tolist()
+        idx_h = both[cut[0]:cut[1]].clone().view(torch.int32).view(Q, k)
+        val_h = both[cut[1]:cut[2]].clone().view(Q, k)
+        span_h = both[cut[2]:cut[3]].clone().view(torch.int32).view(P, n, 2)
+        score_h = both[cut[3]:cut[4]].clone().view(P, n)
+        null_h = both[cut[4]:cut[5]].clone()
+        cap = self.S - 2
+        answers: List[List[Dict[str, object]]] = []
+        tok_cache: Dict[int, Tuple[bytes, list]] = {}
+        for q in range(Q):
+            row = []
+            for f, s in zip(idx_h[q].tolist(), val_h[q].tolist()):
+                if f < 0 or s == float("-inf"):
+                    break  # sorted: nothing after a padding entry or a -inf score
+                pair, slot = goff[q] + f // n, f % n
+                t0, t1 = span_h[pair, slot].tolist()
+                if pair not in tok_cache or len(tok_cache[pair][1]) <= t1:
+                    p = passages[pair]
+                    full = bytes(p) if isinstance(p, (bytes, bytearray)) else p.encode("utf-8")
+                    cutrow = full[:self.max_row_bytes]
+                    need = min(cap, t1 + 1)  # the row is tokenized only as far as the span's last token
+                    toks = (self.vocab.token_spans(cutrow, need) if self.vocab is not None
+                            else token_spans(cutrow, self.cfg.vocab_size, need))
+                    tok_cache[pair] = (full, toks)
+                full, toks = tok_cache[pair]
+                a, b = toks[t0][0], toks[t1][1]
+                start, end, text = self._char_span(full, a, b)
+                row.append({"passage": pair - goff[q], "start": start, "end": end, "text": text, "score": float(s),
+                            "null_score": float(null_h[pair]), "tokens": (int(t0), int(t1))})
+            answers.append(row)
+        return AnswerResult(Q, P, answers, span_h, score_h, null_h)
+
+    def answer_pairs(self, questions: Sequence, passages: Sequence, goff: Sequence[int], top_k: int = 3,
+                     max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None) -> "AnswerResult":
+        """:meth:`span_pairs` with ``n_best = top_k``, then :meth:`rank_spans`: a reader over every
+        (question, passage) pair, each question's best ``top_k`` answer spans over all of its passages (a
+        question's top-k holds at most ``top_k`` spans of one pair)."""
+        span, score, null = self.span_pairs(questions, passages, goff, top_k, max_answer_tokens, max_query_tokens)
+        return self.rank_spans(span, score, null, passages, goff, top_k)
 
     def rank_scores(self, scores: torch.Tensor, goff: Sequence[int], top_k: int = 10,
                     activation: str = "none") -> RerankResult:
@@ -768,6 +933,11 @@ class ClassifyEngine:
         extra += sum(o.numel() * o.element_size() for _, o in egraphs)
         # rerank: its query slot, pair rows and type ids (nothing until the first rerank call)
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_rr", None) or {}).values() if t.is_cuda)
+        # answer: the [P, n] span buffers, the span head's fp32 forms and its graphs' static outputs
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_an", None) or ()))
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self.model, "_span_inputs", None) or {}).values())
+        extra += sum(o.numel() * o.element_size() for k, (_, outs) in (getattr(self, "_bgraphs", None) or {}).items()
+                     if k[0] == "answer" for o in outs)
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

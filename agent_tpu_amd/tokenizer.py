@@ -52,9 +52,16 @@ atpu-pair v1 — cross-encoder rows ``[CLS] query [SEP] passage [SEP]`` with the
 ``token_type_ids``, assembled from the single-segment rows of either tokenizer
 (:func:`pair_rows`; HIP kernel ``csrc/kernels/rerank.hip``, bit-for-bit). The spec is
 the docstring of :func:`pair_rows`.
+
+Token byte offsets — the tokenizers return ids only; :func:`token_spans` (hash) and
+:meth:`WordPieceVocab.token_spans` give, host side only, the ``(byte_start, byte_end)`` of every id
+that ``token_ids`` returns for the same row and cap: a hash piece or a matched WordPiece piece gets
+its own bytes, a word that becomes ``[UNK]`` the whole word. ``map_answer`` maps answer token spans
+to characters with them.
 """
 from __future__ import annotations
 
+import re
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -75,6 +82,7 @@ def _byte_class(c: int) -> int:
 
 
 _CLASS = bytes(_byte_class(c) for c in range(256))
+_WORDS = re.compile(b"\x01|\x02+")  # on a row translated by _CLASS: one punctuation byte, or a run of word bytes
 
 
 def _fnv(h: int, data: bytes) -> int:
@@ -112,6 +120,20 @@ def token_ids(row: bytes, vocab: int, cap: int) -> List[int]:
             out.append(FIRST_HASH_ID + h % mod)
         i = j
     return out
+
+
+def token_spans(row: bytes, vocab: int, cap: int) -> List[Tuple[int, int]]:
+    """``(byte_start, byte_end)`` in ``row`` of every id :func:`token_ids` returns for the same ``row``
+    and ``cap`` (``vocab`` only keeps the signatures alike): a punctuation byte, or a piece of at
+    most 24 bytes of a word."""
+    out: List[Tuple[int, int]] = []
+    for m in _WORDS.finditer(bytes(row).translate(_CLASS)):  # the words, found on the row's byte classes
+        i, j = m.span()
+        for b0 in range(i, j, PIECE_BYTES):
+            if len(out) >= cap:
+                return out
+            out.append((b0, min(j, b0 + PIECE_BYTES)))
+    return out[:cap]
 
 
 def tokenize_rows(rows: Sequence[bytes], seq_len: int, vocab: int,
@@ -193,7 +215,8 @@ class WordPieceVocab:
         return len(self.entries)
 
     # -------------------------------------------------------------- Python twin
-    def _match(self, word: bytes) -> Optional[List[int]]:
+    def _match(self, word: bytes, ends: Optional[List[int]] = None) -> Optional[List[int]]:
+        """Greedy longest-match ids of ``word``; ``ends``, when given, receives each piece's end byte."""
         out: List[int] = []
         s, n = 0, len(word)
         while s < n:
@@ -208,6 +231,8 @@ class WordPieceVocab:
             if hit is None:
                 return None
             out.append(hit)
+            if ends is not None:
+                ends.append(e)
             s = e
         return out
 
@@ -217,6 +242,28 @@ class WordPieceVocab:
             return [self.unk_id]
         got = self._match(word.lower() if self.lowercase else word)  # bytes.lower() folds ASCII only
         return [self.unk_id] if got is None else got
+
+    def word_spans(self, word: bytes) -> List[Tuple[int, int]]:
+        """``(start, end)`` within ``word`` of every id :meth:`word_ids` returns: a matched piece gets its
+        own bytes, a word that becomes ``[UNK]`` the whole word."""
+        if len(word) > MAX_WORD_CHARS and sum(word.translate(_NOT_CONT)) > MAX_WORD_CHARS:
+            return [(0, len(word))]
+        ends: List[int] = []
+        if self._match(word.lower() if self.lowercase else word, ends) is None:  # lower() keeps byte positions
+            return [(0, len(word))]
+        return list(zip([0] + ends[:-1], ends))
+
+    def token_spans(self, row: bytes, cap: int) -> List[Tuple[int, int]]:
+        """``(byte_start, byte_end)`` in ``row`` of every id :meth:`token_ids` returns for the same ``row``
+        and ``cap``."""
+        out: List[Tuple[int, int]] = []
+        row = bytes(row)
+        for m in _WORDS.finditer(row.translate(_CLASS)):
+            if len(out) >= cap:
+                break
+            i, j = m.span()
+            out.extend((i + a, i + b) for a, b in self.word_spans(row[i:j]))
+        return out[:cap]
 
     def token_ids(self, row: bytes, cap: int) -> List[int]:
         """Token ids of one row (no specials), at most ``cap`` of them."""

@@ -246,9 +246,10 @@ METRICS = Metrics()
 
 
 # --------------------------------------------------------------- profile
-GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_summarize",
+GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_summarize",
            "risk_accumulate"}
-BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_summarize"}
+BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer",
+             "map_summarize"}
 
 
 def gpu_health(caps: List[str]) -> Optional[Dict[str, Any]]:

@@ -57,6 +57,7 @@ OP_TO_MODULE: Dict[str, str] = {
     "map_embed": "map_embed",
     "map_search": "map_search",
     "map_rerank": "map_rerank",
+    "map_answer": "map_answer",
     "map_summarize": "map_summarize",
     # outbound side effects (opt-in only)
     "trigger_oracle": "trigger_oracle",

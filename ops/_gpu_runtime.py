@@ -18,7 +18,10 @@ vocabulary: its texts are then tokenized by ``atpu-wordpiece v1`` instead of the
 hash tokenizer.
 ``"head": "none"`` in that json marks an encoder without pooler and classifier (a plain
 ``BertModel`` export): the file need not hold ``pool_*`` / ``cls_*``, ``map_embed`` serves it
-and ``map_classify`` refuses it.
+and ``map_classify`` refuses it. ``"head": "qa"`` marks a ``BertForQuestionAnswering`` export: the file
+holds ``qa_w`` / ``qa_b`` (the span head ``map_answer`` needs), ``pool_*`` / ``cls_*`` are optional as for
+``"none"``, and ``map_classify`` / ``map_rerank`` refuse it the same way. ``?qa=1`` on a preset adds a
+random-init span head next to the pooler and classifier.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -52,6 +55,7 @@ class ModelSpec:
     vocab: Optional[str] = None  # vocab.txt of the model: the WordPiece tokenizer; None: the hash tokenizer
     lowercase: bool = True  # uncased vocabulary: ASCII A-Z folded before matching
     head: bool = True  # False ("head": "none" in the json): an encoder without pooler / classifier (map_embed only)
+    qa: bool = False  # a span head ("?qa=1", or "head": "qa" in the json, which also clears ``head``): map_answer
 
 
 def _flag(value: Any) -> bool:
@@ -74,7 +78,8 @@ def parse_spec(path: str) -> ModelSpec:
     if base in PRESETS:
         return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
                          int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
-                         vocab=vocab, lowercase=True if lowercase is None else lowercase)
+                         vocab=vocab, lowercase=True if lowercase is None else lowercase,
+                         qa=_flag(q.get("qa", "0")))
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
@@ -84,9 +89,10 @@ def parse_spec(path: str) -> ModelSpec:
             vocab = os.path.join(os.path.dirname(os.path.abspath(base)), str(meta["vocab"]))  # absolute stays
         if lowercase is None:
             lowercase = _flag(meta.get("lowercase", True))
+        head = str(meta.get("head", "classifier")).strip().lower()
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
                          file=base, quant=quant, vocab=vocab, lowercase=lowercase,
-                         head=str(meta.get("head", "classifier")).strip().lower() != "none")
+                         head=head not in ("none", "qa"), qa=head == "qa")
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -175,7 +181,7 @@ def _build_handle(model_path: str, device) -> GpuHandle:
 
     def local():
         spec = parse_spec(model_path)
-        cfg = config_for(spec.preset, num_labels=spec.labels)
+        cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa)
         box.update(spec=spec, cfg=cfg)
         # the vocabulary is read and its table built on every rank (same file, same node: no
         # broadcast), before the weights, so a missing or bad file on any rank fails the load on all
