@@ -426,6 +426,17 @@ PYBIND11_MODULE(_atpu, m) {
                     P<const int32_t>(type_ids), P<const int32_t>(lens), P<int32_t>(span), P<float>(score),
                     P<float>(null), P<float>(logits), B, Sq, H, max_len, n, S(stream));
         });
+  m.def("tag_entities",
+        [](uintptr_t x, uintptr_t fin, uintptr_t u, uintptr_t su, uintptr_t c, uintptr_t lens, uintptr_t label_type,
+           uintptr_t label_begin, uintptr_t ids, uintptr_t cont, uintptr_t ent, uintptr_t ent_sum, uintptr_t count,
+           uintptr_t label_out, uintptr_t prob_out, uintptr_t logits_out, int B, int Sq, int H, int L, int V,
+           int mode, int E, uintptr_t stream) {
+          tag_entities(P<const bf16>(x), P<const float>(fin), P<const float>(u), P<const float>(su),
+                       P<const float>(c), P<const int32_t>(lens), P<const int32_t>(label_type),
+                       P<const int32_t>(label_begin), P<const int32_t>(ids), P<const uint8_t>(cont),
+                       P<int32_t>(ent), P<float>(ent_sum), P<int32_t>(count), P<int32_t>(label_out),
+                       P<float>(prob_out), P<float>(logits_out), B, Sq, H, L, V, mode, E, S(stream));
+        });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

@@ -339,6 +339,28 @@ void span_topk(const bf16* x, const float* fin, const float* u, const float* su,
                const int32_t* type_ids, const int32_t* lens, int32_t* span, float* score, float* null, float* logits,
                int B, int S, int H, int max_len, int n, hipStream_t stream);
 
+// ------------------------------------------- token classification (tag_head.hip)
+// A label per text token j in [1, len - 2] of the rows x [B*S, H] ([CLS] text [SEP]) and the row's
+// grouped entities. Logits as span_topk: with fin [B*S, 2] the rows are raw and logit_c[j] =
+// rstd_j (x_j . u_c) - (rstd_j mu_j) su_c + c_c, without it x_j . u_c + c_c. u [L, H], su [L], c [L]
+// fp32. y_j = argmax (logit desc, label asc, a NaN ranks as -inf, all NaN: 0), p_j = 1 / sum_c
+// exp(logit_c - max) (a NaN adds 0; all NaN: p = 0). label_type [L] (-1: outside) and label_begin
+// [L] drive the grouping: mode 0 one record per tagged token (first, first, label, 1); mode 1 a
+// group starts when type >= 0 and (j == 1 or the type changes or begin) and runs to the next
+// start or type change; mode 2 the same on word heads: a token with cont[ids[b, j]] != 0 (ids
+// outside [0, V) and token 1: never) takes its head's label, never starts, always extends, and
+// is not scored. ent [B, E, 4] = (first, last, type, n) text-relative, ent_sum [B, E] the fp32 sum
+// of the n probabilities in token order; the first E groups in token order, count [B] the true
+// number, unused slots (-1, -1, -1, 0) and 0.0. Optional (null: not written): label_out [B, S]
+// (-1 outside the text), prob_out [B, S] (0 outside), logits_out [B, S, L] (-inf outside).
+// ids / cont are read in mode 2 only. 3 <= S <= 512, H % 64 == 0 in [64, 1024], L in [1, 64],
+// E in [1, 512]; B == 0: no launch.
+void tag_entities(const bf16* x, const float* fin, const float* u, const float* su, const float* c,
+                  const int32_t* lens, const int32_t* label_type, const int32_t* label_begin, const int32_t* ids,
+                  const uint8_t* cont, int32_t* ent, float* ent_sum, int32_t* count, int32_t* label_out,
+                  float* prob_out, float* logits_out, int B, int S, int H, int L, int V, int mode, int E,
+                  hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

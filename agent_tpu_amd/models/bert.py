@@ -41,6 +41,7 @@ class BertConfig:
     num_labels: int = 2
     eps: float = 1e-12
     qa_head: bool = False  # a span head (HF BertForQuestionAnswering qa_outputs) after the classifier
+    tag_labels: int = 0  # > 0: a token classification head of that many labels after the other heads
 
     @property
     def head_dim(self) -> int:
@@ -53,6 +54,8 @@ class BertConfig:
         head = H * H + H + self.num_labels * H + self.num_labels
         if self.qa_head:
             head += 2 * H + 2
+        if self.tag_labels > 0:
+            head += self.tag_labels * H + self.tag_labels
         return emb + L * layer + head
 
     def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True,
@@ -127,6 +130,9 @@ def param_specs(cfg: BertConfig):
     if cfg.qa_head:
         yield "qa_w", (2, H), bf
         yield "qa_b", (2,), f32
+    if cfg.tag_labels > 0:
+        yield "tag_w", (cfg.tag_labels, H), bf
+        yield "tag_b", (cfg.tag_labels,), f32
 
 
 def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: float = 0.0,
@@ -153,11 +159,14 @@ def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: flo
     return pack
 
 
-def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPack:
+def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor], head: str = "sequence") -> ParamPack:
     """Build a pack from a transformers ``BertForSequenceClassification`` state dict, from a
     ``BertForQuestionAnswering`` one (``qa_outputs``; no pooler, no classifier; ``cfg.qa_head``), or from
     a plain ``BertModel`` one (no ``bert.`` prefix, no classifier, the pooler optional): head
-    tensors the dict does not have stay zero."""
+    tensors the dict does not have stay zero. ``head="token"``: a ``BertForTokenClassification`` dict
+    (no pooler), whose ``classifier.*`` is the tag head (``cfg.tag_labels``), not the row classifier."""
+    if head not in ("sequence", "token"):
+        raise ValueError("head must be 'sequence' or 'token'")
     pack = ParamPack(param_specs(cfg))
     if "embeddings.word_embeddings.weight" in sd and "bert.embeddings.word_embeddings.weight" not in sd:
         sd = {"bert." + k: v for k, v in sd.items()}
@@ -185,8 +194,9 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor]) -> ParamPac
         put(f"l{i}.f2_b", sd[b + "output.dense.bias"])
         put(f"l{i}.ln2_g", sd[b + "output.LayerNorm.weight"])
         put(f"l{i}.ln2_b", sd[b + "output.LayerNorm.bias"])
+    cls = ("tag_w", "tag_b") if head == "token" else ("cls_w", "cls_b")
     for name, key in (("pool_w", "bert.pooler.dense.weight"), ("pool_b", "bert.pooler.dense.bias"),
-                      ("cls_w", "classifier.weight"), ("cls_b", "classifier.bias"),
+                      (cls[0], "classifier.weight"), (cls[1], "classifier.bias"),
                       ("qa_w", "qa_outputs.weight"), ("qa_b", "qa_outputs.bias")):
         if key in sd and name in pack:
             put(name, sd[key])
@@ -260,6 +270,11 @@ class BertClassifier:
         # runs the same kernel on the normalised rows
         self.answer_fused = os.getenv("ATPU_ANSWER_FUSED", "1") not in ("0", "false", "no")
         self._span_inputs: Optional[Dict[str, torch.Tensor]] = None
+        # token labels on the folded encoder: the last LayerNorm folded into the tag head by
+        # tag_entities (ops/tag.py); ATPU_TAG_FUSED=0 finishes every row with ops.layernorm and
+        # runs the same kernel on the normalised rows
+        self.tag_fused = os.getenv("ATPU_TAG_FUSED", "1") not in ("0", "false", "no")
+        self._tag_inputs: Optional[Dict[str, torch.Tensor]] = None
 
     # ------------------------------------------------------------ LN folding
     def folded(self) -> Dict[str, torch.Tensor]:
@@ -561,6 +576,45 @@ class BertClassifier:
         h = self.encode(ids, lens, type_ids, cls_only_last=False)
         return ops.span_topk(h, lens, type_ids, B, si["w"], si["z"], si["b"], max_answer_tokens, n_best,
                              logits_out=logits_out)
+
+    # ------------------------------------------------------------ token classification
+    def tag_inputs(self) -> Dict[str, torch.Tensor]:
+        """The tag head as ``ops.tag_entities`` takes it (fp32, built once, on the device; build it
+        outside graph capture). Fused with the last layer's LayerNorm: ``u [T, H] = ln2_g * tag_w``,
+        ``su [T]`` = the row sums of ``u`` and ``c [T] = ln2_b . tag_w + tag_b``, both accumulated in fp64
+        and rounded once. Unfused: ``w`` = ``tag_w`` as fp32, ``b`` = ``tag_b``."""
+        if self.cfg.tag_labels <= 0:
+            raise ValueError("model has no tag head")
+        if self._tag_inputs is None:
+            p = self.p
+            ln2 = f"l{self.cfg.layers - 1}."
+            w = p["tag_w"].float().contiguous()
+            b = p["tag_b"].float().contiguous()
+            u = (p[ln2 + "ln2_g"].float().view(1, -1) * w).contiguous()
+            su = u.double().sum(1).float().contiguous()
+            c = ((p[ln2 + "ln2_b"].double().view(1, -1) * w.double()).sum(1) + b.double()).float().contiguous()
+            self._tag_inputs = {"u": u, "su": su, "c": c, "w": w, "b": b}
+        return self._tag_inputs
+
+    def tags(self, ids: torch.Tensor, lens: torch.Tensor, label_type: torch.Tensor, label_begin: torch.Tensor,
+             mode: int, max_entities: int, type_ids: Optional[torch.Tensor] = None,
+             cont: Optional[torch.Tensor] = None, **outs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Entities of single-segment rows ``[CLS] text [SEP]``: ``(ent [B, E, 4] int32, ent_sum [B, E]
+        fp32, count [B] int32)`` of :func:`ops.tag_entities` (``mode`` 0 / 1 / 2 = tokens / simple / first;
+        mode 2 needs the vocabulary's continuation table ``cont``). ``outs``: the kernel's optional
+        outputs (``ent``, ``ent_sum``, ``count``, ``label_out``, ``prob_out``, ``logits_out``).
+
+        Every layer runs in full. On the folded encoder the final LayerNorm is not run over the rows
+        but folded into the tag head (``tag_entities`` with ``fin``)."""
+        B, S = ids.shape
+        ti = self.tag_inputs()
+        if ids.is_cuda and self.tag_fused and self.can_fold(B, S):
+            g, fin, _ = self.encode_folded(ids, lens, type_ids, raw=True)
+            return ops.tag_entities(g, lens, B, S, ti["u"], ti["su"], ti["c"], label_type, label_begin, mode,
+                                    max_entities, fin=fin, ids=ids, cont=cont, **outs)
+        h = self.encode(ids, lens, type_ids, cls_only_last=False)
+        return ops.tag_entities(h, lens, B, S, ti["w"], None, ti["b"], label_type, label_begin, mode, max_entities,
+                                ids=ids, cont=cont, **outs)
 
     def head(self, h: torch.Tensor, B: int, S: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Pooler + classifier + softmax/top-k (K7) over encoder states ``h``."""

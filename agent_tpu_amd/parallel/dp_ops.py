@@ -628,6 +628,39 @@ def answer_batch_task(payload: Dict[str, Any]) -> Any:
     return ma.answer_batch(h, payloads, rank, ws)
 
 
+# ------------------------------------------------------------------ map_tag
+@dp_task("map_tag")
+def tag_task(payload: Dict[str, Any]) -> Any:
+    """One map_tag job: the texts split contiguously over the ranks, each rank tagging its slice, the
+    per-row ent / ent_sum / count records all-gathered (C2) after the error exchange and mapped to
+    character offsets on rank 0 (:func:`ops.map_tag.tag_batch` with one job)."""
+    from ops import map_tag as mt
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    res = mt.tag_batch(h, [payload], rank, ws)
+    if rank != 0:
+        return None
+    kind, value = res[0]
+    if kind == "err":
+        raise value
+    return value
+
+
+@dp_task("map_tag_batch")
+def tag_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several map_tag jobs of one lease (same model, aggregation and max_entities): one collective
+    model load, then :func:`ops.map_tag.tag_batch` on every rank."""
+    from ops import map_tag as mt
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    payloads = payload["payloads"]
+    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    return mt.tag_batch(h, payloads, rank, ws)
+
+
 # ---------------------------------------------------------- risk_accumulate
 def _local_values(payload: Dict[str, Any], rank: int, ws: int) -> Tuple[torch.Tensor, int]:
     """This rank's slice of a ``values`` / ``items`` payload, as fp64 (CSV payloads stream

@@ -72,6 +72,19 @@ class AnswerResult:
 
 
 @dataclass
+class TagResult:
+    rows: int
+    # per row, in token order. Grouped modes: {"entity_group", "score", "word", "start", "end"}; mode "none":
+    # {"entity", "score", "index", "word", "start", "end"} with index = the token's position in the row,
+    # [CLS] being 0. start / end are character offsets into the row's text; score = ent_sum / n in fp64
+    entities: List[List[Dict[str, object]]]
+    counts: List[int]        # per row: the true number of groups
+    truncated: List[int]     # the rows whose count exceeded max_entities
+    ent: torch.Tensor        # [rows, E, 4] int32 (host): (first, last, type, n), (-1, -1, -1, 0) past the last
+    ent_sum: torch.Tensor    # [rows, E] fp32 (host)
+
+
+@dataclass
 class RunStats:
     rows: int = 0
     batches: int = 0
@@ -882,6 +895,165 @@ class ClassifyEngine:
         question's top-k holds at most ``top_k`` spans of one pair)."""
         span, score, null = self.span_pairs(questions, passages, goff, top_k, max_answer_tokens, max_query_tokens)
         return self.rank_spans(span, score, null, passages, goff, top_k)
+
+    # ------------------------------------------------------------ token classification (map_tag)
+    # Single-segment rows [CLS] text [SEP] on the machinery of embed_texts: per chunk of at most B rows
+    # one H2D through the pinned rows, one captured graph per ("tag", bucket, mode, E) (tokenize,
+    # model.tags) and D2D copies of the records into [N, E] buffers; one D2H per call. The host maps
+    # the token positions to character offsets. Text past seq_len - 2 tokens is not tagged.
+    TAG_NEEDS_VOCAB = "aggregation 'first' needs a WordPiece vocabulary (the hash tokenizer has no word pieces)"
+
+    def set_tag_labels(self, names: Optional[Sequence[str]] = None, outside: Sequence[str] = ("O",)) -> None:
+        """Name the tag head's labels (default: ``ops.default_tag_names``) and build the label tables."""
+        L = self.cfg.tag_labels
+        if L <= 0:
+            raise ValueError("model has no tag head")
+        names = ops.default_tag_names(L) if names is None else [str(n) for n in names]
+        if len(names) != L:
+            raise ValueError(f"tag_labels: {len(names)} names for a head of {L} labels")
+        types, lt, lb = ops.tag_tables(names, outside)
+        self._tag = {"names": names, "types": types, "label_type": lt.to(self.device),
+                     "label_begin": lb.to(self.device)}
+
+    def _tag_state(self) -> Dict[str, object]:
+        if getattr(self, "_tag", None) is None:
+            self.set_tag_labels()
+        return self._tag
+
+    def _tag_cont(self) -> Optional[torch.Tensor]:
+        """``cont [V]`` uint8: 1 where the vocabulary's entry is a ``##`` piece (built once per engine)."""
+        if self.vocab is None:
+            raise ValueError(self.TAG_NEEDS_VOCAB)
+        if getattr(self, "_tagcont", None) is None:
+            flags = np.fromiter((len(e) > 2 and e.startswith(b"##") for e in self.vocab.entries), dtype=np.uint8,
+                                count=len(self.vocab))
+            self._tagcont = torch.from_numpy(flags).to(self.device)
+        return self._tagcont
+
+    @staticmethod
+    def _check_tag_args(mode, max_entities) -> Tuple[int, int]:
+        if isinstance(mode, str):
+            if mode not in ops.tag.MODES:
+                raise ValueError("aggregation must be 'simple', 'first' or 'none'")
+            mode = ops.tag.MODES[mode]
+        if isinstance(mode, bool) or not isinstance(mode, int) or mode not in (0, 1, 2):
+            raise ValueError("aggregation must be 'simple', 'first' or 'none'")
+        E = max_entities
+        if isinstance(E, bool) or not isinstance(E, int) or not 1 <= E <= ops.tag.MAX_ENTITIES:
+            raise ValueError("max_entities must be an int in [1, 512]")
+        return mode, E
+
+    def _tag_step(self, bucket: int, mode: int, E: int):
+        st = self._tag_state()
+        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+        return self.model.tags(self.ids_s[0][:bucket], self.lens_s[0][:bucket], st["label_type"], st["label_begin"],
+                               mode, E, cont=self._tag_cont() if mode == 2 else None)
+
+    def _tag_bucket(self, bucket: int, mode: int, E: int):
+        if not self.use_graph:
+            return self._tag_step(bucket, mode, E)
+        gk = ("tag", bucket, mode, E)
+        if gk not in self._bgraphs:
+            self.model.tag_inputs()  # built here, not inside the capture
+            self._warm(lambda: self._tag_step(bucket, mode, E))
+            self._bgraphs[gk] = capture_graph(lambda: self._tag_step(bucket, mode, E), pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def tag_rows(self, rows: Sequence, mode="simple", max_entities: int = 64
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The entity records of every row: ``(ent [N, E, 4] int32, ent_sum [N, E] fp32, count [N] int32)`` of
+        ``ops.tag_entities``, left on the engine's device (a DP caller all-gathers them): views of the
+        engine's ``[N, E]`` buffers, valid until the next call."""
+        mode, E = self._check_tag_args(mode, max_entities)
+        if self.S < 3:
+            raise ValueError("tag_texts needs seq_len >= 3")
+        self._tag_state()
+        if mode == 2:
+            self._tag_cont()
+        N, dev = len(rows), self.device
+        if getattr(self, "_tg", None) is None or self._tg[0].shape[0] < N or self._tg[0].shape[1] != E:
+            cap = max(N, self.B)  # one allocation serves every job of up to B rows
+            self._tg = (torch.empty((cap, E, 4), dtype=torch.int32, device=dev),
+                        torch.empty((cap, E), dtype=torch.float32, device=dev),
+                        torch.empty((cap,), dtype=torch.int32, device=dev))
+        ent, ent_sum, count = (t[:N] for t in self._tg)
+        for b0 in range(0, N, self.B):
+            chunk = self._encode_rows(rows[b0:b0 + self.B])
+            text, offs = pack_rows(chunk)
+            n = len(chunk)
+            if dev.type == "cuda":
+                pin = self._pinned()
+                bk = self._bucket(n)
+                pin["text"][:text.size].copy_(torch.from_numpy(text))
+                pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
+                pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
+                if text.size:
+                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
+                self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
+                e, s_, c = self._tag_bucket(bk, mode, E)
+                ent[b0:b0 + n].copy_(e[:n]), ent_sum[b0:b0 + n].copy_(s_[:n]), count[b0:b0 + n].copy_(c[:n])
+                torch.cuda.current_stream(dev).synchronize()  # the pinned rows are free again
+            else:
+                ids, lens = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
+                st = self._tag_state()
+                e, s_, c = self.model.tags(ids, lens, st["label_type"], st["label_begin"], mode, E,
+                                           cont=self._tag_cont() if mode == 2 else None)
+                ent[b0:b0 + n].copy_(e), ent_sum[b0:b0 + n].copy_(s_), count[b0:b0 + n].copy_(c)
+        return ent, ent_sum, count
+
+    def map_tags(self, ent: torch.Tensor, ent_sum: torch.Tensor, count: torch.Tensor, rows: Sequence,
+                 mode="simple") -> "TagResult":
+        """Records -> entities on the host: one D2H, then the token positions of every record are mapped to
+        character offsets of its row (``token_spans``, the row cut at ``max_row_bytes`` as the device cut it,
+        tokenized only as far as the row's last record) and ``score = ent_sum / n`` in fp64."""
+        mode, _ = self._check_tag_args(mode, 1)
+        st = self._tag_state()
+        N, E = int(ent.shape[0]), int(ent.shape[1])
+        if len(rows) != N:
+            raise ValueError("map_tags: one row of text per record row")
+        if N == 0:
+            return TagResult(0, [], [], [], ent.cpu(), ent_sum.cpu())
+        both = torch.cat([ent.view(torch.float32).reshape(-1), ent_sum.reshape(-1),
+                          count.view(torch.float32).reshape(-1)]).cpu()  # one D2H, one sync
+        ent_h = both[:N * E * 4].clone().view(torch.int32).view(N, E, 4)
+        sum_h = both[N * E * 4:N * E * 5].clone().view(N, E)
+        counts = both[N * E * 5:].clone().view(torch.int32).tolist()
+        cap = self.S - 2
+        entities: List[List[Dict[str, object]]] = []
+        for i in range(N):
+            k = min(counts[i], E)
+            recs, sums = ent_h[i, :k].tolist(), sum_h[i, :k].tolist()
+            row: List[Dict[str, object]] = []
+            if k:
+                r = rows[i]
+                full = bytes(r) if isinstance(r, (bytes, bytearray)) else r.encode("utf-8")
+                cutrow = full[:self.max_row_bytes]
+                need = min(cap, recs[-1][1] + 1)  # records are in token order: the last one ends last
+                toks = (self.vocab.token_spans(cutrow, need) if self.vocab is not None
+                        else token_spans(cutrow, self.cfg.vocab_size, need))
+                ascii_row = full.isascii()  # bytes are characters: nothing to widen, no prefix to decode
+                for (first, last, third, n), s in zip(recs, sums):
+                    if ascii_row:
+                        start, end = toks[first][0], toks[last][1]
+                        word = full[start:end].decode("ascii")
+                    else:
+                        start, end, word = self._char_span(full, toks[first][0], toks[last][1])
+                    score = float(np.float64(s) / np.float64(n)) if n > 0 else 0.0
+                    if mode == 0:
+                        row.append({"entity": st["names"][third], "score": score, "index": first + 1, "word": word,
+                                    "start": start, "end": end})
+                    else:
+                        row.append({"entity_group": st["types"][third], "score": score, "word": word,
+                                    "start": start, "end": end})
+            entities.append(row)
+        return TagResult(N, entities, counts, [i for i in range(N) if counts[i] > E], ent_h, sum_h)
+
+    def tag_texts(self, rows: Sequence, mode="simple", max_entities: int = 64) -> "TagResult":
+        """:meth:`tag_rows`, then :meth:`map_tags`: the entities of an in-memory list of strings."""
+        ent, ent_sum, count = self.tag_rows(rows, mode, max_entities)
+        return self.map_tags(ent, ent_sum, count, rows, mode)
 
     def rank_scores(self, scores: torch.Tensor, goff: Sequence[int], top_k: int = 10,
                     activation: str = "none") -> RerankResult:

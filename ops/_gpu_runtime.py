@@ -22,6 +22,10 @@ and ``map_classify`` refuses it. ``"head": "qa"`` marks a ``BertForQuestionAnswe
 holds ``qa_w`` / ``qa_b`` (the span head ``map_answer`` needs), ``pool_*`` / ``cls_*`` are optional as for
 ``"none"``, and ``map_classify`` / ``map_rerank`` refuse it the same way. ``?qa=1`` on a preset adds a
 random-init span head next to the pooler and classifier.
+``"head": "token"`` marks a ``BertForTokenClassification`` export: the file holds ``tag_w`` / ``tag_b`` (the
+tag head ``map_tag`` needs), the json names its labels in ``"tag_labels": [...]`` (``"outside": ["O"]`` by
+default), ``pool_*`` / ``cls_*`` are optional, and ``map_classify`` / ``map_rerank`` / ``map_answer`` refuse it.
+``?tags=N`` on a preset adds a random-init tag head of ``N`` labels named ``O, B-T0, I-T0, B-T1, ...``.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -56,12 +60,22 @@ class ModelSpec:
     lowercase: bool = True  # uncased vocabulary: ASCII A-Z folded before matching
     head: bool = True  # False ("head": "none" in the json): an encoder without pooler / classifier (map_embed only)
     qa: bool = False  # a span head ("?qa=1", or "head": "qa" in the json, which also clears ``head``): map_answer
+    tags: int = 0  # labels of a tag head ("?tags=N", or "head": "token" in the json, which clears ``head``): map_tag
+    tag_names: Optional[Tuple[str, ...]] = None  # "tag_labels" of the json; None: ops.default_tag_names
+    tag_outside: Tuple[str, ...] = ("O",)
 
 
 def _flag(value: Any) -> bool:
     if isinstance(value, str):
         return value.strip().lower() not in ("0", "false", "no", "")
     return bool(value)
+
+
+def _tags(value: Any) -> int:
+    n = int(value)
+    if not 0 <= n <= 64:
+        raise ValueError("a tag head has 1 to 64 labels")
+    return n
 
 
 def parse_spec(path: str) -> ModelSpec:
@@ -79,7 +93,7 @@ def parse_spec(path: str) -> ModelSpec:
         return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
                          int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
                          vocab=vocab, lowercase=True if lowercase is None else lowercase,
-                         qa=_flag(q.get("qa", "0")))
+                         qa=_flag(q.get("qa", "0")), tags=_tags(q.get("tags", "0")))
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
@@ -90,9 +104,18 @@ def parse_spec(path: str) -> ModelSpec:
         if lowercase is None:
             lowercase = _flag(meta.get("lowercase", True))
         head = str(meta.get("head", "classifier")).strip().lower()
+        names, outside = None, ("O",)
+        if head == "token":
+            names = meta.get("tag_labels")
+            if not isinstance(names, list) or not names or not all(isinstance(n, str) for n in names):
+                raise ValueError(f'{base}.json: "head": "token" needs "tag_labels": a list of label names')
+            _tags(len(names))
+            names = tuple(names)
+            outside = tuple(str(n) for n in meta.get("outside", ["O"]))
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
                          file=base, quant=quant, vocab=vocab, lowercase=lowercase,
-                         head=head not in ("none", "qa"), qa=head == "qa")
+                         head=head not in ("none", "qa", "token"), qa=head == "qa",
+                         tags=len(names) if names else 0, tag_names=names, tag_outside=outside)
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -181,7 +204,7 @@ def _build_handle(model_path: str, device) -> GpuHandle:
 
     def local():
         spec = parse_spec(model_path)
-        cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa)
+        cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa, tag_labels=spec.tags)
         box.update(spec=spec, cfg=cfg)
         # the vocabulary is read and its table built on every rank (same file, same node: no
         # broadcast), before the weights, so a missing or bad file on any rank fails the load on all
@@ -203,6 +226,8 @@ def _build_handle(model_path: str, device) -> GpuHandle:
         batch = spec.batch_rows or _auto_batch_rows(spec.preset, spec.seq_len)
         eng = ClassifyEngine(cfg, pack, device, batch_rows=batch, seq_len=spec.seq_len,
                              topk=min(cfg.num_labels, 64), quant=spec.quant, vocab=box["vocab"])
+        if spec.tags:
+            eng.set_tag_labels(spec.tag_names, spec.tag_outside)
         sync()
         h = GpuHandle(spec, cfg, eng)
         t2 = time.perf_counter()
