@@ -421,11 +421,25 @@ PYBIND11_MODULE(_atpu, m) {
   m.def("span_topk",
         [](uintptr_t x, uintptr_t fin, uintptr_t u, uintptr_t su, uintptr_t c, uintptr_t type_ids, uintptr_t lens,
            uintptr_t span, uintptr_t score, uintptr_t null, uintptr_t logits, int B, int Sq, int H, int max_len, int n,
-           uintptr_t stream) {
+           uintptr_t stream, uintptr_t own) {
           span_topk(P<const bf16>(x), P<const float>(fin), P<const float>(u), P<const float>(su), P<const float>(c),
                     P<const int32_t>(type_ids), P<const int32_t>(lens), P<int32_t>(span), P<float>(score),
-                    P<float>(null), P<float>(logits), B, Sq, H, max_len, n, S(stream));
+                    P<float>(null), P<float>(logits), B, Sq, H, max_len, n, S(stream), P<const int32_t>(own));
         });
+  m.def("window_assemble",
+        [](uintptr_t ids_q, uintptr_t lens_q, uintptr_t ids_p, uintptr_t lens_p, uintptr_t qidx, uintptr_t win_pair,
+           uintptr_t win_start, uintptr_t ids, uintptr_t type_ids, uintptr_t lens, uintptr_t own, int R, int Pp, int Q,
+           int Sq, int L, int mq, int stride, int cls, int sep, int pad, uintptr_t stream) {
+          window_assemble(P<const int32_t>(ids_q), P<const int32_t>(lens_q), P<const int32_t>(ids_p),
+                          P<const int32_t>(lens_p), P<const int32_t>(qidx), P<const int32_t>(win_pair),
+                          P<const int32_t>(win_start), P<int32_t>(ids), P<int32_t>(type_ids), P<int32_t>(lens),
+                          P<int32_t>(own), R, Pp, Q, Sq, L, mq, stride, cls, sep, pad, S(stream));
+        });
+  m.def("window_best", [](uintptr_t span_w, uintptr_t score_w, uintptr_t null_w, uintptr_t start_w, uintptr_t wrow,
+                          uintptr_t span, uintptr_t score, uintptr_t null, int R, int rows, int n, uintptr_t stream) {
+    window_best(P<const int32_t>(span_w), P<const float>(score_w), P<const float>(null_w), P<const int32_t>(start_w),
+                P<const int32_t>(wrow), P<int32_t>(span), P<float>(score), P<float>(null), R, rows, n, S(stream));
+  });
   m.def("tag_entities",
         [](uintptr_t x, uintptr_t fin, uintptr_t u, uintptr_t su, uintptr_t c, uintptr_t lens, uintptr_t label_type,
            uintptr_t label_begin, uintptr_t ids, uintptr_t cont, uintptr_t ent, uintptr_t ent_sum, uintptr_t count,

@@ -335,9 +335,32 @@ void group_topk(const float* scores, const int32_t* goff, int32_t* idx, float* v
 // span [B, n, 2] passage-relative (i - lo, j - lo), score [B, n]; exhausted slots (-1, -1), -inf.
 // null [B] = logit_0[0] + logit_1[0]; logits [B, S, 2] optional (null: not written).
 // 4 <= S <= 512, H % 64 == 0 in [64, 1024], n in [1, 32], max_len in [1, S]; B == 0: no launch.
+// own [B, 2] int32 (optional, null: none): row b proposes only starts i with lo + clamp(own0, 0, S)
+// <= i < lo + clamp(own1, 0, S) (the window rows of window.hip); without it the launch is unchanged.
 void span_topk(const bf16* x, const float* fin, const float* u, const float* su, const float* c,
                const int32_t* type_ids, const int32_t* lens, int32_t* span, float* score, float* null, float* logits,
-               int B, int S, int H, int max_len, int n, hipStream_t stream);
+               int B, int S, int H, int max_len, int n, hipStream_t stream, const int32_t* own = nullptr);
+
+// ------------------------------------------- windows over long passages (window.hip)
+// Window rows "atpu-window v1" (agent_tpu_amd/tokenizer.py window_rows is the twin). Window row r of
+// pair p = clamp(win_pair[r], 0, Pp-1), question q = clamp(qidx[p], 0, Q-1), starting at passage
+// token a = clamp(win_start[r], 0, max(T-1, 0)): [CLS] q_tok[0:nq] [SEP] p_tok[a : a+nw] [SEP] [PAD]...
+// with nq = min(lens_q[q]-2, mq, S-3), cap = S-3-nq, T = lens_p[p]-2 (lens clamped into [2, S] /
+// [2, L]; ids_q [Q, S], ids_p [Pp, L]), nw = min(cap, T-a); type_ids and lens as pair_assemble.
+// own [R, 2] = the window-relative starts the row owns: step = min(stride, cap), h = (cap-step)/2,
+// own0 = a == 0 ? 0 : h, own1 = a + cap >= T ? nw : step + h. Nothing outside the R rows is touched.
+void window_assemble(const int32_t* ids_q, const int32_t* lens_q, const int32_t* ids_p, const int32_t* lens_p,
+                     const int32_t* qidx, const int32_t* win_pair, const int32_t* win_start, int32_t* ids,
+                     int32_t* type_ids, int32_t* lens, int32_t* own, int R, int Pp, int Q, int S, int L, int mq,
+                     int stride, int cls, int sep, int pad, hipStream_t stream);
+// The n best of every pair's window rows wrow[p] .. wrow[p+1]-1 (wrow [P+1], clamped into [0, R]) of
+// span_w [R, n, 2] / score_w [R, n], ordered by (value desc, (row, slot) asc), a NaN ranks and is
+// returned as -inf: span [P, n, 2] = the pick's span + start_w[row] (an exhausted slot stays (-1, -1)),
+// score [P, n]; past the last element (-1, -1), -inf. null [P] = fminf over the rows' null_w in row
+// order (+inf for no rows). n in [1, 32], R >= 1, R * n < 2^31.
+void window_best(const int32_t* span_w, const float* score_w, const float* null_w, const int32_t* start_w,
+                 const int32_t* wrow, int32_t* span, float* score, float* null, int R, int P, int n,
+                 hipStream_t stream);
 
 // ------------------------------------------- token classification (tag_head.hip)
 // A label per text token j in [1, len - 2] of the rows x [B*S, H] ([CLS] text [SEP]) and the row's

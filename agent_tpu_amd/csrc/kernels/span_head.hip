@@ -25,6 +25,10 @@
 // r - 1's pick, the scheme of group_topk_kernel: wave w scans the starts lo + w, lo + w + 8, ...,
 // its lanes the ends; the wave's best by the butterfly, the 8 waves' bests through LDS in wave
 // order. Once a round finds nothing the remaining slots are (-1, -1) with -inf.
+//
+// own [B, 2] (optional; the OWN instantiations): the window rows of window.hip let a row propose only
+// the spans whose start it owns: lo + clamp(own0, 0, S) <= i < lo + clamp(own1, 0, S). Ends, ids, the
+// order and the passage-relative output are unchanged. Without own the kernel is the one it was.
 #include "atpu/common.h"
 #include "atpu/kernels.h"
 #include "atpu/topk.h"
@@ -51,12 +55,12 @@ __device__ __forceinline__ void dot8(const u32x4& v, const float (&w0)[8], const
   }
 }
 
-template <bool FIN>
+template <bool FIN, bool OWN>
 __global__ __launch_bounds__(kSpanThreads) void span_topk_kernel(
     const bf16* __restrict__ x, const float* __restrict__ fin, const float* __restrict__ u,
     const float* __restrict__ su, const float* __restrict__ c, const int32_t* __restrict__ type_ids,
     const int32_t* __restrict__ lens, int32_t* __restrict__ span, float* __restrict__ score, float* __restrict__ null,
-    float* __restrict__ logits, int S, int H, int max_len, int n) {
+    float* __restrict__ logits, const int32_t* __restrict__ own, int S, int H, int max_len, int n) {
   __shared__ __attribute__((aligned(16))) float us[2 * kSpanMaxH];  // u [2][H]
   __shared__ float l0[kSpanMaxS], l1[kSpanMaxS];                    // start / end logits
   __shared__ float redv[2][kSpanWaves];
@@ -138,6 +142,9 @@ __global__ __launch_bounds__(kSpanThreads) void span_topk_kernel(
 #pragma unroll
   for (int w = 0; w < kSpanWaves; ++w) lo = min(lo, lo_w[w]);
   const int hi = len - 2;  // lo in [0, S], hi in [0, S - 2]: every LDS index below lies in [0, S)
+  // the starts this row may propose: [i_lo, i_hi] inside [lo, hi] (own is device data: clamped)
+  const int i_lo = OWN ? lo + min(max(own[2 * b], 0), S) : lo;
+  const int i_hi = OWN ? min(hi, lo + min(max(own[2 * b + 1], 0), S) - 1) : hi;
   int32_t* sp = span + (size_t)b * n * 2;
   float* sc = score + (size_t)b * n;
   float pv = __builtin_inff();  // the previous pick: everything comes after (+inf, -1)
@@ -146,7 +153,7 @@ __global__ __launch_bounds__(kSpanThreads) void span_topk_kernel(
   for (; r < n; ++r) {
     float bv = ninf;
     int bi = kSpanNoIdx;
-    for (int i = lo + wave; i <= hi; i += kSpanWaves) {  // wave-uniform
+    for (int i = i_lo + wave; i <= i_hi; i += kSpanWaves) {  // wave-uniform
       const float a = l0[i];
       const int w = min(max_len, hi - i + 1);
       for (int d = lane; d < w; d += kWave) {
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(kSpanThreads) void span_topk_kernel(
 
 void span_topk(const bf16* x, const float* fin, const float* u, const float* su, const float* c,
                const int32_t* type_ids, const int32_t* lens, int32_t* span, float* score, float* null, float* logits,
-               int B, int S, int H, int max_len, int n, hipStream_t stream) {
+               int B, int S, int H, int max_len, int n, hipStream_t stream, const int32_t* own) {
   ATPU_CHECK(S >= 4 && S <= kSpanMaxS, "span_topk: S must be in [4, 512]");
   ATPU_CHECK(H % 64 == 0 && H >= 64 && H <= kSpanMaxH, "span_topk: H must be a multiple of 64 in [64, 1024]");
   ATPU_CHECK(n >= 1 && n <= 32, "span_topk: n must be in [1, 32]");
@@ -213,12 +220,18 @@ void span_topk(const bf16* x, const float* fin, const float* u, const float* su,
   ATPU_CHECK(x && u && su && c && type_ids && lens && span && score && null, "span_topk: null tensor");
   ATPU_CHECK(((reinterpret_cast<uintptr_t>(x) & 15) | (reinterpret_cast<uintptr_t>(fin) & 7) |
               (reinterpret_cast<uintptr_t>(u) & 3)) == 0, "span_topk: x must be 16-byte and fin 8-byte aligned");
-  if (fin)
-    hipLaunchKernelGGL((span_topk_kernel<true>), dim3(B), dim3(kSpanThreads), 0, stream, x, fin, u, su, c, type_ids,
-                       lens, span, score, null, logits, S, H, max_len, n);
+#define ATPU_SPAN_LAUNCH(FIN, OWN)                                                                               \
+  hipLaunchKernelGGL((span_topk_kernel<FIN, OWN>), dim3(B), dim3(kSpanThreads), 0, stream, x, fin, u, su, c, type_ids, \
+                     lens, span, score, null, logits, own, S, H, max_len, n)
+  if (fin && own)
+    ATPU_SPAN_LAUNCH(true, true);
+  else if (fin)
+    ATPU_SPAN_LAUNCH(true, false);
+  else if (own)
+    ATPU_SPAN_LAUNCH(false, true);
   else
-    hipLaunchKernelGGL((span_topk_kernel<false>), dim3(B), dim3(kSpanThreads), 0, stream, x, fin, u, su, c, type_ids,
-                       lens, span, score, null, logits, S, H, max_len, n);
+    ATPU_SPAN_LAUNCH(false, false);
+#undef ATPU_SPAN_LAUNCH
   ATPU_HIP_CHECK(hipGetLastError());
 }
 

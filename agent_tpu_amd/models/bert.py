@@ -559,11 +559,12 @@ class BertClassifier:
         return self._span_inputs
 
     def spans(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, max_answer_tokens: int,
-              n_best: int, logits_out: Optional[torch.Tensor] = None
+              n_best: int, logits_out: Optional[torch.Tensor] = None, own: Optional[torch.Tensor] = None
               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Answer spans of pair rows (``ops.pair_assemble``): ``(span [B, n_best, 2] int32 passage-relative
         token spans, score [B, n_best] fp32, null [B] fp32)`` of :func:`ops.span_topk`; ``logits_out
-        [B, S, 2]`` fp32, when given, receives the start / end logits.
+        [B, S, 2]`` fp32, when given, receives the start / end logits; ``own [B, 2]`` int32, when given
+        (window rows, ``ops.window_assemble``), restricts every row's span starts to the range it owns.
 
         Every layer runs in full. On the folded encoder the final LayerNorm is not run over the rows
         but folded into the span head (``span_topk`` with ``fin``)."""
@@ -572,10 +573,10 @@ class BertClassifier:
         if ids.is_cuda and self.answer_fused and self.can_fold(B, S):
             g, fin, _ = self.encode_folded(ids, lens, type_ids, raw=True)
             return ops.span_topk(g, lens, type_ids, B, si["u"], si["su"], si["c"], max_answer_tokens, n_best,
-                                 fin=fin, logits_out=logits_out)
+                                 fin=fin, logits_out=logits_out, own=own)
         h = self.encode(ids, lens, type_ids, cls_only_last=False)
         return ops.span_topk(h, lens, type_ids, B, si["w"], si["z"], si["b"], max_answer_tokens, n_best,
-                             logits_out=logits_out)
+                             logits_out=logits_out, own=own)
 
     # ------------------------------------------------------------ token classification
     def tag_inputs(self) -> Dict[str, torch.Tensor]:

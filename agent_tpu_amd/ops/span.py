@@ -19,6 +19,10 @@ the candidates are ``(i, j)`` with ``lo <= i <= j <= hi`` and ``j - i < max_len`
 ``group_topk``: value descending, then ``i * S + j`` ascending; ``+0.0`` and ``-0.0`` tie. Spans are
 passage-relative ``(i - lo, j - lo)``; exhausted slots are ``(-1, -1)`` with ``-inf``.
 ``null[b] = logit_0[0] + logit_1[0]`` is the score of "no answer in this passage".
+
+``own [B, 2]`` int32, optional (the window rows of ``ops.window_assemble``): row ``b`` proposes only the
+spans whose start it owns, ``lo + clamp(own[b, 0], 0, S) <= i < lo + clamp(own[b, 1], 0, S)``; ends, order
+and output are unchanged. Without it the launch is the one it always was.
 """
 from __future__ import annotations
 
@@ -56,12 +60,13 @@ def span_logits_ref(x: torch.Tensor, lens: torch.Tensor, B: int, u: torch.Tensor
 
 
 def span_select_ref(logits: torch.Tensor, type_ids: torch.Tensor, lens: torch.Tensor, max_len: int,
-                    n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                    n: int, own: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The selection of the kernel on given fp32 ``logits [B, S, 2]`` -> ``(span [B, n, 2] int32,
     score [B, n] fp32, null [B] fp32)`` on the CPU. A stable descending sort of the candidates in id
-    order gives (value desc, id asc)."""
+    order gives (value desc, id asc). ``own [B, 2]``: the owned window-relative starts, see the module."""
     lg = logits.detach().float().cpu()
     B, S, _ = lg.shape
+    ow = None if own is None else own.detach().cpu().view(-1, 2)[:B].to(torch.int64).clamp(0, S).tolist()
     types = type_ids.detach().cpu().view(-1, S)[:B]
     ln = lens.detach().cpu().reshape(-1)[:B].to(torch.int64).clamp(2, S).tolist()
     span = torch.full((B, n, 2), -1, dtype=torch.int32)
@@ -75,6 +80,8 @@ def span_select_ref(logits: torch.Tensor, type_ids: torch.Tensor, lens: torch.Te
         lo = int(one[0]) if one.numel() else S
         hi = ln[b] - 2
         ok = (ii >= lo) & (jj >= ii) & (jj <= hi) & (jj - ii < max_len)
+        if ow is not None:
+            ok = ok & (ii >= lo + ow[b][0]) & (ii < lo + ow[b][1])
         ids = ok.view(-1).nonzero().view(-1)  # ascending i * S + j
         if not ids.numel():
             continue
@@ -90,11 +97,12 @@ def span_select_ref(logits: torch.Tensor, type_ids: torch.Tensor, lens: torch.Te
 
 
 def span_topk_ref(x: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, B: int, u: torch.Tensor,
-                  su: torch.Tensor, c: torch.Tensor, max_len: int, n: int, fin: Optional[torch.Tensor] = None
+                  su: torch.Tensor, c: torch.Tensor, max_len: int, n: int, fin: Optional[torch.Tensor] = None,
+                  own: Optional[torch.Tensor] = None
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """PyTorch twin of the kernel -> ``(span, score, null, logits)`` on the CPU (also the CPU path)."""
     lg = span_logits_ref(x, lens, B, u, su, c, fin).float().cpu()
-    return span_select_ref(lg, type_ids, lens, max_len, n) + (lg,)
+    return span_select_ref(lg, type_ids, lens, max_len, n, own) + (lg,)
 
 
 def _out(t: Optional[torch.Tensor], shape, dtype, device, name: str) -> torch.Tensor:
@@ -108,12 +116,13 @@ def _out(t: Optional[torch.Tensor], shape, dtype, device, name: str) -> torch.Te
 def span_topk(x: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, B: int, u: torch.Tensor, su: torch.Tensor,
               c: torch.Tensor, max_len: int, n: int, fin: Optional[torch.Tensor] = None,
               span: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
-              null: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None
-              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              null: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
+              own: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``(span [B, n, 2] int32, score [B, n] fp32, null [B] fp32)`` of the hidden rows ``x [B*S, H]`` (raw
     rows when ``fin [B*S, 2]`` is given, else normalised rows), ``lens [B]`` and ``type_ids [B, S]`` int32,
     the head ``u [2, H]``, ``su [2]``, ``c [2]`` fp32. Given outputs may hold more than ``B`` rows; rows
-    past ``B`` are not touched. ``logits_out [B, S, 2]`` fp32, when given, receives the logits."""
+    past ``B`` are not touched. ``logits_out [B, S, 2]`` fp32, when given, receives the logits. ``own
+    [>=B, 2]`` int32, when given, restricts every row's span starts to the range it owns."""
     check(isinstance(B, int) and B >= 0, "span_topk: B must be an int >= 0")
     check(x.dim() == 2 and (B == 0 or x.shape[0] % B == 0), "span_topk: x must be [B*S, H]")
     H = int(x.shape[1])
@@ -130,7 +139,10 @@ def span_topk(x: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, B: in
     check(tuple(u.shape) == (2, H) and su.numel() == 2 and c.numel() == 2, "span_topk: u [2, H], su [2], c [2]")
     if fin is not None:
         check(tuple(fin.shape) == (B * S, 2) and fin.dtype == torch.float32, "span_topk: fin must be fp32 [B*S, 2]")
-    same_device(x, fin, u, su, c, lens, type_ids, span, score, null, logits_out)
+    if own is not None:
+        check(own.dtype == torch.int32 and own.is_contiguous() and own.dim() == 2 and own.shape[1] == 2
+              and own.shape[0] >= B, "span_topk: own must be contiguous int32 [B, 2]")
+    same_device(x, fin, u, su, c, lens, type_ids, span, score, null, logits_out, own)
     dev = x.device
     span = _out(span, (B, n, 2), torch.int32, dev, "span")
     score = _out(score, (B, n), torch.float32, dev, "score")
@@ -140,7 +152,7 @@ def span_topk(x: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, B: in
     if B == 0:
         return span, score, null
     if not x.is_cuda:
-        sp, sc, nl, lg = span_topk_ref(x, lens, type_ids, B, u, su, c, max_len, n, fin)
+        sp, sc, nl, lg = span_topk_ref(x, lens, type_ids, B, u, su, c, max_len, n, fin, own)
         span[:B].copy_(sp), score[:B].copy_(sc), null[:B].copy_(nl)
         if logits_out is not None:
             logits_out[:B].copy_(lg)
@@ -151,5 +163,5 @@ def span_topk(x: torch.Tensor, lens: torch.Tensor, type_ids: torch.Tensor, B: in
         check(t.dtype == torch.float32 and t.is_contiguous(), f"span_topk: {name} must be contiguous fp32")
     native().span_topk(ptr(x), ptr(fin) if fin is not None else 0, ptr(u), ptr(su), ptr(c), ptr(type_ids), ptr(lens),
                        ptr(span), ptr(score), ptr(null), ptr(logits_out) if logits_out is not None else 0, B, S, H,
-                       max_len, n, launch_stream(x))
+                       max_len, n, launch_stream(x), ptr(own) if own is not None else 0)
     return span, score, null

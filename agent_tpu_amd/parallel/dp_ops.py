@@ -600,7 +600,9 @@ def rerank_batch_task(payload: Dict[str, Any]) -> Any:
 def answer_task(payload: Dict[str, Any]) -> Any:
     """One map_answer job: the (question, passage) pairs split contiguously over the ranks, each rank
     reading its slice, the per-pair span / score / null rows all-gathered (C2) after the error exchange
-    and ranked on rank 0 (:func:`ops.map_answer.answer_batch` with one job)."""
+    and ranked on rank 0 (:func:`ops.map_answer.answer_batch` with one job). With ``doc_stride`` each rank
+    reads its pairs' windows and folds them per pair before the gather, so the collective is unchanged but
+    for one ``[P]`` int32 row of window counts."""
     from ops import map_answer as ma
     from ops._gpu_runtime import get_gpu_handle, get_model_path
 
@@ -617,7 +619,7 @@ def answer_task(payload: Dict[str, Any]) -> Any:
 
 @dp_task("map_answer_batch")
 def answer_batch_task(payload: Dict[str, Any]) -> Any:
-    """Several map_answer jobs of one lease (same model, max_query_tokens and max_answer_tokens): one
+    """Several map_answer jobs of one lease (same model, max_query_tokens, max_answer_tokens and doc_stride): one
     collective model load, then :func:`ops.map_answer.answer_batch` on every rank."""
     from ops import map_answer as ma
     from ops._gpu_runtime import get_gpu_handle, get_model_path

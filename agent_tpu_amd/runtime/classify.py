@@ -31,7 +31,7 @@ from .._native import native
 from ..models.bert import BertClassifier, BertConfig
 from ..models.params import ParamPack
 from ..tokenizer import (CLS_ID, DEFAULT_MAX_ROW_BYTES, PAD_ID, SEP_ID, WordPieceVocab, default_max_query_tokens,
-                         pack_rows, token_spans)
+                         pack_rows, token_spans, window_table)
 from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
@@ -69,6 +69,7 @@ class AnswerResult:
     span: torch.Tensor   # [pairs, n, 2] int32 (host): every pair's n best token spans, (-1, -1) past the last
     score: torch.Tensor  # [pairs, n] fp32 (host)
     null: torch.Tensor   # [pairs] fp32 (host)
+    window_count: Optional[int] = None  # with doc_stride: the window rows this call read
 
 
 @dataclass
@@ -164,12 +165,14 @@ class ClassifyEngine:
 
     # ------------------------------------------------------------ device step
     def _tokenize(self, text: torch.Tensor, offs: torch.Tensor, ids: Optional[torch.Tensor] = None,
-                  lens: Optional[torch.Tensor] = None, rows: Optional[int] = None):
-        """K1 of this engine: the model's WordPiece vocabulary when it has one, else the hash tokenizer."""
+                  lens: Optional[torch.Tensor] = None, rows: Optional[int] = None, seq_len: Optional[int] = None):
+        """K1 of this engine: the model's WordPiece vocabulary when it has one, else the hash tokenizer.
+        ``seq_len``: the row width (default: the engine's ``S``)."""
+        S = self.S if seq_len is None else seq_len
         if self.vocab is not None:
-            return ops.tokenize_wordpiece(text, offs, self.S, self.vocab, self.max_row_bytes,
+            return ops.tokenize_wordpiece(text, offs, S, self.vocab, self.max_row_bytes,
                                           ids=ids, lens=lens, rows=rows)
-        return ops.tokenize(text, offs, self.S, self.cfg.vocab_size, self.max_row_bytes,
+        return ops.tokenize(text, offs, S, self.cfg.vocab_size, self.max_row_bytes,
                             ids=ids, lens=lens, rows=rows)
 
     def _step(self, slot: int, rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -707,13 +710,15 @@ class ClassifyEngine:
                 scores[c0:c0 + m].copy_(self._rerank_bucket(bk, mq, label)[:m])
         return scores
 
-    def _pair_chunks(self, queries: Sequence, passages: Sequence, goff: List[int], mq: int):
+    def _pair_chunks(self, queries: Sequence, passages: Sequence, goff: List[int], mq: int, wide: bool = False):
         """The chunk staging of the pair jobs (:meth:`score_pairs`, :meth:`span_pairs`): yields
         ``(c0, m, bucket, rows)`` per chunk of at most ``B`` pairs. On the GPU the chunk's packed texts,
         offsets (padding rows: empty passages of query 0) and query indices are copied through the
         pinned rows into slot 0 and the query slot, ``rows`` is None and the caller runs its step on
         ``bucket`` rows; on the CPU ``rows`` is the assembled ``(ids, type_ids, lens)``. Before a
-        chunk's pinned rows are overwritten the copies of the previous one have completed (``free``)."""
+        chunk's pinned rows are overwritten the copies of the previous one have completed (``free``).
+        ``wide`` (the windowed reader): on the CPU ``rows`` is ``(ids_q, lens_q, ids_p, lens_p, qidx)`` with
+        the passages tokenized whole, at ``L = max_row_bytes + 2``, and not assembled."""
         Q, P = len(queries), len(passages)
         cuda = self.device.type == "cuda"
         if P == 0:
@@ -730,6 +735,11 @@ class ClassifyEngine:
             local = local.astype(np.int32)
             if not cuda:
                 ids_q, lens_q = self._tokenize(torch.from_numpy(text_q), torch.from_numpy(offs_q))
+                if wide:
+                    ids_p, lens_p = self._tokenize(torch.from_numpy(text_p), torch.from_numpy(offs_p),
+                                                   seq_len=self.max_row_bytes + 2)
+                    yield c0, m, None, (ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local))
+                    continue
                 ids_p, lens_p = self._tokenize(torch.from_numpy(text_p), torch.from_numpy(offs_p))
                 yield c0, m, None, ops.pair_assemble(ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local), mq,
                                                      *self._special_ids())
@@ -798,15 +808,24 @@ class ClassifyEngine:
         return top_k, ma, mq
 
     def span_pairs(self, questions: Sequence, passages: Sequence, goff: Sequence[int], n_best: int = 3,
-                   max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None
-                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                   max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None,
+                   doc_stride: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The ``n_best`` answer spans of every (question, passage) pair: ``(span [P, n, 2] int32
         passage-relative token spans, score [P, n] fp32, null [P] fp32)`` of ``ops.span_topk``, left on the
         engine's device (a DP caller all-gathers them): views of the engine's ``[P, n]`` buffers, valid until
-        the next call. The pair layout is that of :meth:`score_pairs`."""
+        the next call. The pair layout is that of :meth:`score_pairs`.
+
+        ``doc_stride`` (an int in ``[1, S - 3]``): a passage too long for its row is read in overlapping
+        windows ("atpu-window v1", ``tokenizer.window_table``) that advance by ``min(doc_stride, cap)``
+        tokens; the windows' spans are folded back per pair (``ops.window_best``), ``span`` then being
+        passage-absolute tokens of the passage cut at ``max_row_bytes`` and ``null`` the minimum over the
+        pair's windows. ``self.window_counts`` holds every pair's window count, ``[P]`` int32."""
         Q, P = len(questions), len(passages)
         goff = self._check_goff(goff, Q, P)
         n, ma, mq = self._check_answer_args(n_best, max_answer_tokens, max_query_tokens)
+        if doc_stride is not None and (isinstance(doc_stride, bool) or not isinstance(doc_stride, int)
+                                       or not 1 <= doc_stride <= self.S - 3):
+            raise ValueError("doc_stride must be an int in [1, seq_len - 3]")
         dev = self.device
         if getattr(self, "_an", None) is None or self._an[0].shape[0] < P or self._an[0].shape[1] != n:
             rows = max(P, self.B)  # one allocation serves every job of up to B pairs
@@ -814,6 +833,9 @@ class ClassifyEngine:
                         torch.empty((rows, n), dtype=torch.float32, device=dev),
                         torch.empty((rows,), dtype=torch.float32, device=dev))
         span, score, null = (t[:P] for t in self._an)
+        if doc_stride is not None:
+            self._span_windows(questions, passages, goff, n, ma, mq, doc_stride, span, score, null)
+            return span, score, null
         for c0, m, bk, rows in self._pair_chunks(questions, passages, goff, mq):
             if rows is not None:
                 ids, types, lens = rows
@@ -822,6 +844,139 @@ class ClassifyEngine:
                 sp, sc, nl = self._answer_bucket(bk, mq, ma, n)
             span[c0:c0 + m].copy_(sp[:m]), score[c0:c0 + m].copy_(sc[:m]), null[c0:c0 + m].copy_(nl[:m])
         return span, score, null
+
+    # ------------------------------------------------------- answer: windows over long passages
+    # With doc_stride a pair chunk takes two kinds of graph. ("wtok", bucket) tokenizes the chunk's
+    # questions at S and its passages whole, at L = max_row_bytes + 2 (a token covers at least one
+    # byte, so only the byte cut truncates). The two length vectors come back in one D2H (the call's
+    # one sync per pair chunk), the host lays out the window table, and per chunk of at most B window
+    # rows ("wanswer", bucket, mq, max_len, n, doc_stride) runs window_assemble and model.spans(own=)
+    # on the table's rows; their spans are copied D2D into [R, n] buffers and one window_best launch
+    # folds them into the chunk's slice of the per-pair buffers. Padding window rows are windows of
+    # pair 0 at start 0; they lie outside every pair's row range.
+    def _window_bufs(self) -> Dict[str, torch.Tensor]:
+        if getattr(self, "_wn", None) is None:
+            dev, B = self.device, self.B
+            L = self.max_row_bytes + 2
+
+            def i32(*shape, **kw):
+                return torch.zeros(shape, dtype=torch.int32, **kw)
+
+            w = {"ids_p": i32(B, L, device=dev), "lens_p": i32(B, device=dev), "win_pair": i32(B, device=dev),
+                 "win_start": i32(B, device=dev), "own": i32(B, 2, device=dev), "wrow": i32(B + 1, device=dev)}
+            if dev.type == "cuda":
+                w.update(pin_pair=i32(B, pin_memory=True), pin_start=i32(B, pin_memory=True),
+                         pin_wrow=i32(B + 1, pin_memory=True))
+            self._wn = w
+        return self._wn
+
+    def _wtok_step(self, bucket: int) -> None:
+        r, w = self._rerank_bufs(), self._window_bufs()
+        self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
+        self._tokenize(self.text[0], self.offs[0], ids=w["ids_p"], lens=w["lens_p"], rows=bucket,
+                       seq_len=self.max_row_bytes + 2)
+
+    def _wtok_bucket(self, bucket: int) -> None:
+        if not self.use_graph:
+            return self._wtok_step(bucket)
+        gk = ("wtok", bucket)
+        if gk not in self._bgraphs:
+            self._warm(lambda: self._wtok_step(bucket))
+            self._bgraphs[gk] = capture_graph(lambda: self._wtok_step(bucket), pool=self._bpool)
+        self._bgraphs[gk][0].replay()
+
+    def _wanswer_step(self, bucket: int, mq: int, max_len: int, n: int, doc_stride: int):
+        r, w = self._rerank_bufs(), self._window_bufs()
+        cls_id, sep_id, pad_id = self._special_ids()
+        ops.window_assemble(r["ids_q"], r["lens_q"], w["ids_p"], w["lens_p"], r["qidx"], w["win_pair"],
+                            w["win_start"], mq, doc_stride, cls_id, sep_id, pad_id, ids=r["ids"],
+                            type_ids=r["type_ids"], lens=r["lens"], own=w["own"], rows=bucket)
+        return self.model.spans(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], max_len, n,
+                                own=w["own"])
+
+    def _wanswer_bucket(self, bucket: int, mq: int, max_len: int, n: int, doc_stride: int):
+        if not self.use_graph:
+            return self._wanswer_step(bucket, mq, max_len, n, doc_stride)
+        gk = ("wanswer", bucket, mq, max_len, n, doc_stride)
+        if gk not in self._bgraphs:
+            self.model.span_inputs()  # built here, not inside the capture
+            self._warm(lambda: self._wanswer_step(bucket, mq, max_len, n, doc_stride))
+            self._bgraphs[gk] = capture_graph(lambda: self._wanswer_step(bucket, mq, max_len, n, doc_stride),
+                                              pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def _window_rows_bufs(self, R: int, n: int) -> Tuple[torch.Tensor, ...]:
+        """``(span_w [R, n, 2], score_w [R, n], null_w [R], start_w [R])`` for a pair chunk's window rows:
+        grown here, outside any capture."""
+        if getattr(self, "_wr", None) is None or self._wr[0].shape[0] < R or self._wr[0].shape[1] != n:
+            rows, dev = max(R, 2 * self.B), self.device
+            self._wr = (torch.empty((rows, n, 2), dtype=torch.int32, device=dev),
+                        torch.empty((rows, n), dtype=torch.float32, device=dev),
+                        torch.empty((rows,), dtype=torch.float32, device=dev),
+                        torch.empty((rows,), dtype=torch.int32, device=dev))
+        return tuple(t[:R] for t in self._wr)
+
+    def _span_windows(self, questions: Sequence, passages: Sequence, goff: List[int], n: int, ma: int, mq: int,
+                      doc_stride: int, span: torch.Tensor, score: torch.Tensor, null: torch.Tensor) -> None:
+        """The windowed form of :meth:`span_pairs`: fills the per-pair ``span / score / null [P]`` views."""
+        S, B, L = self.S, self.B, self.max_row_bytes + 2
+        P = len(passages)
+        counts = np.zeros(P, dtype=np.int32)
+        r, w = self._rerank_bufs(), self._window_bufs()
+        wfree = None  # the event after which the pinned table rows may be overwritten
+        for c0, m, bk, rows in self._pair_chunks(questions, passages, goff, mq, wide=True):
+            if rows is not None:
+                ids_q, lens_q, ids_p, lens_p, qidx = rows
+                lq, lp, qi = lens_q.tolist(), lens_p.tolist(), qidx.tolist()
+            else:
+                self._wtok_bucket(bk)
+                host = torch.cat([r["lens_q"][:bk], w["lens_p"][:bk], r["qidx"][:bk]]).cpu()  # one D2H, one sync
+                lq, lp, qi = (host[i * bk:(i + 1) * bk].tolist() for i in range(3))
+            pair_l, start_l, wrow = [], [], [0]
+            for i in range(m):
+                nq = min(min(max(lq[qi[i]], 2), S) - 2, mq, S - 3)
+                table = window_table(min(max(lp[i], 2), L) - 2, nq, S, doc_stride)
+                pair_l += [i] * len(table)
+                start_l += [t[0] for t in table]
+                wrow.append(len(pair_l))
+            R = len(pair_l)
+            counts[c0:c0 + m] = np.diff(np.asarray(wrow))
+            win_pair = torch.tensor(pair_l, dtype=torch.int32)
+            win_start = torch.tensor(start_l, dtype=torch.int32)
+            wrow_t = torch.tensor(wrow, dtype=torch.int32)
+            if rows is not None:
+                ids, types, lens, own = ops.window_assemble(ids_q, lens_q, ids_p, lens_p, qidx, win_pair, win_start,
+                                                            mq, doc_stride, *self._special_ids())
+                sp, sc, nl = self.model.spans(ids, lens, types, ma, n, own=own)
+                ops.window_best(sp, sc, nl, win_start, wrow_t, span=span[c0:], score=score[c0:], null=null[c0:])
+                continue
+            span_w, score_w, null_w, start_w = self._window_rows_bufs(R, n)
+            for r0 in range(0, R, B):
+                mw = min(B, R - r0)
+                bkw = self._bucket(mw)
+                if wfree is not None:
+                    wfree.synchronize()
+                w["pin_pair"][:mw].copy_(win_pair[r0:r0 + mw])
+                w["pin_pair"][mw:bkw].zero_()  # padding rows: windows of pair 0 ...
+                w["pin_start"][:mw].copy_(win_start[r0:r0 + mw])
+                w["pin_start"][mw:bkw].zero_()  # ... at start 0, their spans dropped
+                if r0 == 0:
+                    w["pin_wrow"][:m + 1].copy_(wrow_t)
+                    w["wrow"][:m + 1].copy_(w["pin_wrow"][:m + 1], non_blocking=True)
+                w["win_pair"][:bkw].copy_(w["pin_pair"][:bkw], non_blocking=True)
+                w["win_start"][:bkw].copy_(w["pin_start"][:bkw], non_blocking=True)
+                wfree = torch.cuda.Event()
+                wfree.record()
+                sp, sc, nl = self._wanswer_bucket(bkw, mq, ma, n, doc_stride)
+                span_w[r0:r0 + mw].copy_(sp[:mw]), score_w[r0:r0 + mw].copy_(sc[:mw])
+                null_w[r0:r0 + mw].copy_(nl[:mw]), start_w[r0:r0 + mw].copy_(w["win_start"][:mw])
+            ops.window_best(span_w, score_w, null_w, start_w, w["wrow"][:m + 1], span=span[c0:], score=score[c0:],
+                            null=null[c0:])
+        if wfree is not None:
+            wfree.synchronize()
+        self.window_counts = torch.from_numpy(counts).to(self.device)
 
     @staticmethod
     def _char_span(full: bytes, a: int, b: int) -> Tuple[int, int, str]:
@@ -836,12 +991,13 @@ class ClassifyEngine:
         return start, start + len(text), text
 
     def rank_spans(self, span: torch.Tensor, score: torch.Tensor, null: torch.Tensor, passages: Sequence,
-                   goff: Sequence[int], top_k: int = 3) -> "AnswerResult":
+                   goff: Sequence[int], top_k: int = 3, token_cap: Optional[int] = None) -> "AnswerResult":
         """Every question's ``top_k`` best spans over all of its pairs: one ``ops.group_topk`` launch over the
         flattened ``[P * n]`` scores (offsets ``goff * n``; score descending, then pair and slot ascending)
         and one D2H; the token spans of the returned answers are mapped to character offsets of their
         passage on the host (``token_spans``, the row cut at ``max_row_bytes`` as the device cut it).
-        ``-inf`` entries are dropped."""
+        ``-inf`` entries are dropped. ``token_cap``: the most tokens of a passage a span can refer to,
+        ``S - 2`` by default; windowed spans (``doc_stride``) are passage-absolute: pass ``max_row_bytes``."""
         if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
             raise ValueError("top_k must be an int in [1, 32]")
         P, n = int(score.shape[0]), int(score.shape[1])
@@ -862,7 +1018,7 @@ class ClassifyEngine:
         span_h = both[cut[2]:cut[3]].clone().view(torch.int32).view(P, n, 2)
         score_h = both[cut[3]:cut[4]].clone().view(P, n)
         null_h = both[cut[4]:cut[5]].clone()
-        cap = self.S - 2
+        cap = self.S - 2 if token_cap is None else int(token_cap)
         answers: List[List[Dict[str, object]]] = []
         tok_cache: Dict[int, Tuple[bytes, list]] = {}
         for q in range(Q):
@@ -889,12 +1045,19 @@ class ClassifyEngine:
         return AnswerResult(Q, P, answers, span_h, score_h, null_h)
 
     def answer_pairs(self, questions: Sequence, passages: Sequence, goff: Sequence[int], top_k: int = 3,
-                     max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None) -> "AnswerResult":
+                     max_answer_tokens: int = 30, max_query_tokens: Optional[int] = None,
+                     doc_stride: Optional[int] = None) -> "AnswerResult":
         """:meth:`span_pairs` with ``n_best = top_k``, then :meth:`rank_spans`: a reader over every
         (question, passage) pair, each question's best ``top_k`` answer spans over all of its passages (a
-        question's top-k holds at most ``top_k`` spans of one pair)."""
-        span, score, null = self.span_pairs(questions, passages, goff, top_k, max_answer_tokens, max_query_tokens)
-        return self.rank_spans(span, score, null, passages, goff, top_k)
+        question's top-k holds at most ``top_k`` spans of one pair). ``doc_stride``: long passages are read
+        in overlapping windows, see :meth:`span_pairs`."""
+        span, score, null = self.span_pairs(questions, passages, goff, top_k, max_answer_tokens, max_query_tokens,
+                                            doc_stride)
+        if doc_stride is None:
+            return self.rank_spans(span, score, null, passages, goff, top_k)
+        res = self.rank_spans(span, score, null, passages, goff, top_k, token_cap=self.max_row_bytes)
+        res.window_count = int(self.window_counts.sum())
+        return res
 
     # ------------------------------------------------------------ token classification (map_tag)
     # Single-segment rows [CLS] text [SEP] on the machinery of embed_texts: per chunk of at most B rows
@@ -1109,7 +1272,10 @@ class ClassifyEngine:
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_an", None) or ()))
         extra += sum(t.numel() * t.element_size() for t in (getattr(self.model, "_span_inputs", None) or {}).values())
         extra += sum(o.numel() * o.element_size() for k, (_, outs) in (getattr(self, "_bgraphs", None) or {}).items()
-                     if k[0] == "answer" for o in outs)
+                     if k[0] in ("answer", "wanswer") for o in outs)
+        # windowed answer: the long passage rows, the window table and the [R, n] window-row buffers
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_wn", None) or {}).values() if t.is_cuda)
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_wr", None) or ()))
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

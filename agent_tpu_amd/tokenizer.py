@@ -53,6 +53,11 @@ atpu-pair v1 — cross-encoder rows ``[CLS] query [SEP] passage [SEP]`` with the
 (:func:`pair_rows`; HIP kernel ``csrc/kernels/rerank.hip``, bit-for-bit). The spec is
 the docstring of :func:`pair_rows`.
 
+atpu-window v1 — overlapping windows over a passage too long for one pair row (``doc_stride``):
+the window geometry with the start positions each window owns (:func:`window_table`) and the
+window rows (:func:`window_rows`; HIP kernel ``csrc/kernels/window.hip``, bit-for-bit). The spec is
+the docstrings of the two.
+
 Token byte offsets — the tokenizers return ids only; :func:`token_spans` (hash) and
 :meth:`WordPieceVocab.token_spans` give, host side only, the ``(byte_start, byte_end)`` of every id
 that ``token_ids`` returns for the same row and cap: a hash piece or a matched WordPiece piece gets
@@ -377,3 +382,95 @@ def pair_rows(ids_q: np.ndarray, lens_q: np.ndarray, ids_p: np.ndarray, lens_p: 
         types[r, 2 + nq:3 + nq + n_p] = 1
         lens[r] = nq + n_p + 3
     return ids, types, lens
+
+
+# ---------------------------------------------------------------- atpu-window v1
+def window_table(T: int, nq: int, S: int, doc_stride: int) -> List[Tuple[int, int, int, int]]:
+    """atpu-window v1: the windows ``(start, len, own_lo, own_hi)`` of a passage of ``T`` tokens read
+    behind a question of ``nq`` tokens (already cut: ``nq <= S - 3``) in rows of width ``S``. All
+    quantities are passage tokens without specials.
+
+    * ``cap = S - 3 - nq``; ``cap < 1``: one window with an empty passage, ``(0, 0, 0, 0)``;
+    * ``step = min(doc_stride, cap)``, ``h = (cap - step) // 2``;
+    * ``W = 1`` if ``T <= cap`` else ``ceil((T - cap) / step) + 1`` windows, window ``w`` starting at
+      ``a_w = w * step`` with ``len_w = min(cap, T - a_w)`` tokens (0 only when ``T == 0``);
+    * window ``w`` owns the window-relative start positions ``[own_lo, own_hi)``: ``own_lo = 0`` for
+      ``w == 0`` else ``h``; ``own_hi = len_w`` for ``w == W - 1`` else ``step + h``.
+
+    The owned ranges ``[a_w + own_lo, a_w + own_hi)`` partition ``[0, T)`` and each lies inside its
+    window, so a span is a candidate of the one window that owns its start, if it ends inside that
+    window: every span of at most ``ceil((cap - step) / 2) + 1`` tokens does (tested by brute force)."""
+    T, nq, S, doc_stride = int(T), int(nq), int(S), int(doc_stride)
+    if S < 4 or not 0 <= nq <= S - 3 or T < 0 or doc_stride < 1:
+        raise ValueError("window_table: S >= 4, 0 <= nq <= S - 3, T >= 0 and doc_stride >= 1")
+    cap = S - 3 - nq
+    if cap < 1:
+        return [(0, 0, 0, 0)]
+    step = min(doc_stride, cap)
+    h = (cap - step) // 2
+    W = 1 if T <= cap else -(-(T - cap) // step) + 1
+    out = []
+    for w in range(W):
+        a = w * step
+        n = min(cap, T - a)
+        out.append((a, n, 0 if w == 0 else h, n if w == W - 1 else step + h))
+    return out
+
+
+def window_rows(ids_q: np.ndarray, lens_q: np.ndarray, ids_p: np.ndarray, lens_p: np.ndarray, qidx: np.ndarray,
+                win_pair: np.ndarray, win_start: np.ndarray, max_query_tokens: int, doc_stride: int,
+                cls_id: int = CLS_ID, sep_id: int = SEP_ID, pad_id: int = PAD_ID
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """atpu-window v1: the window rows of long passages; pure-Python twin of ``csrc/kernels/window.hip``
+    ``window_assemble_kernel``, bit-for-bit. ``ids_q [Q, S]`` / ``lens_q [Q]`` are question rows,
+    ``ids_p [Pp, L]`` / ``lens_p [Pp]`` the long passage rows (tokenizer output at width ``L``) with their
+    question ``qidx [Pp]``; window row ``r`` reads pair ``p = clamp(win_pair[r], 0, Pp - 1)`` from passage
+    token ``a = clamp(win_start[r], 0, max(T - 1, 0))``:
+
+    * ``nq`` as in :func:`pair_rows`, ``cap = S - 3 - nq``, ``T = clamp(lens_p[p], 2, L) - 2``,
+      ``nw = min(cap, T - a)``;
+    * ``ids = [CLS] q_tok[0:nq] [SEP] p_tok[a:a + nw] [SEP]`` then ``[PAD]``; ``type_ids`` and ``len`` as
+      in :func:`pair_rows`;
+    * ``own = (0 if a == 0 else h, nw if a + cap >= T else step + h)`` with ``step = min(doc_stride,
+      cap)``, ``h = (cap - step) // 2``: on the starts of :func:`window_table` its ``(own_lo, own_hi)``.
+
+    With ``T <= cap`` (one window at 0) ids, type_ids and lens are those of :func:`pair_rows`.
+    Returns ``(ids [R, S], type_ids [R, S], lens [R], own [R, 2])``, all int32."""
+    ids_q, ids_p = np.asarray(ids_q, dtype=np.int32), np.asarray(ids_p, dtype=np.int32)
+    lens_q, lens_p = np.asarray(lens_q, dtype=np.int32), np.asarray(lens_p, dtype=np.int32)
+    qidx = np.asarray(qidx, dtype=np.int32)
+    win_pair, win_start = np.asarray(win_pair, dtype=np.int32), np.asarray(win_start, dtype=np.int32)
+    if ids_q.ndim != 2 or ids_p.ndim != 2:
+        raise ValueError("window_rows: ids_q [Q, S] and ids_p [Pp, L]")
+    (Q, S), (Pp, L) = ids_q.shape, ids_p.shape
+    mq, stride = int(max_query_tokens), int(doc_stride)
+    if S < 4 or L < 2 or Q < 1 or Pp < 1 or mq < 0 or stride < 1:
+        raise ValueError("window_rows: S >= 4, L >= 2, Q >= 1, Pp >= 1, max_query_tokens >= 0 and doc_stride >= 1")
+    if lens_q.shape != (Q,) or lens_p.shape != (Pp,) or qidx.shape != (Pp,):
+        raise ValueError("window_rows: lens_q [Q], lens_p [Pp] and qidx [Pp]")
+    if win_pair.ndim != 1 or win_start.shape != win_pair.shape:
+        raise ValueError("window_rows: win_pair [R] and win_start [R]")
+    R = win_pair.shape[0]
+    ids = np.full((R, S), pad_id, dtype=np.int32)
+    types = np.zeros((R, S), dtype=np.int32)
+    lens = np.zeros(R, dtype=np.int32)
+    own = np.zeros((R, 2), dtype=np.int32)
+    for r in range(R):
+        p = min(max(int(win_pair[r]), 0), Pp - 1)
+        q = min(max(int(qidx[p]), 0), Q - 1)
+        nq = min(min(max(int(lens_q[q]), 2), S) - 2, mq, S - 3)
+        cap = S - 3 - nq
+        T = min(max(int(lens_p[p]), 2), L) - 2
+        a = min(max(int(win_start[r]), 0), max(T - 1, 0))
+        step = min(stride, cap)
+        h = (cap - step) // 2
+        nw = min(cap, T - a)
+        ids[r, 0] = cls_id
+        ids[r, 1:1 + nq] = ids_q[q, 1:1 + nq]
+        ids[r, 1 + nq] = sep_id
+        ids[r, 2 + nq:2 + nq + nw] = ids_p[p, 1 + a:1 + a + nw]
+        ids[r, 2 + nq + nw] = sep_id
+        types[r, 2 + nq:3 + nq + nw] = 1
+        lens[r] = nq + nw + 3
+        own[r] = (0 if a == 0 else h, nw if a + cap >= T else step + h)
+    return ids, types, lens, own

@@ -5,7 +5,8 @@ question together with each of its passages as ``[CLS] question [SEP] passage [S
 ``map_rerank``), a span head gives every token a start and an end logit, and the best answer spans of
 each passage, then of each question over all of its passages, are selected on the GPU
 (``agent_tpu_amd/ops/span.py``, ``group_topk``). The host maps the returned token spans to character
-offsets of the passage. Two payload forms (see map_answer.CONTRACT.md):
+offsets of the passage. With ``doc_stride`` a passage longer than its row is read in overlapping windows
+("atpu-window v1") instead of being cut at the row's end. Two payload forms (see map_answer.CONTRACT.md):
 
 1. one question: ``{"question": "...", "passages": ["...", ...]}``;
 2. several: ``{"questions": ["...", ...], "passages": [["...", ...], ...]}``, one list per question.
@@ -41,6 +42,12 @@ ERRORS: Dict[str, str] = {
     "qa": "model has no QA head",
 }
 
+#: the input errors of the ``doc_stride`` key (also in map_answer.CONTRACT.md); kept apart from
+#: :data:`ERRORS`, whose keys are the errors of a payload without it
+WINDOW_ERRORS: Dict[str, str] = {
+    "doc_stride": "payload.doc_stride must be an integer in [1, seq_len - 3]",
+}
+
 
 class Options(NamedTuple):
     top_k: int
@@ -48,6 +55,7 @@ class Options(NamedTuple):
     max_query_tokens: Optional[int]  # None: the engine's default, min(32, (seq_len - 3) // 2)
     min_score_over_null: Optional[float]
     return_null_scores: bool
+    doc_stride: Optional[int] = None  # None: one row per pair, the passage cut at the row's end
 
 
 def _is_int(v: Any) -> bool:
@@ -75,7 +83,10 @@ def options(payload: Dict[str, Any]) -> Options:
     nulls = payload.get("return_null_scores", False)
     if not isinstance(nulls, bool):
         raise ValueError(ERRORS["return_null_scores"])
-    return Options(top_k, ma, mq, margin, nulls)
+    stride = payload.get("doc_stride")
+    if stride is not None and (not _is_int(stride) or stride < 1):
+        raise ValueError(WINDOW_ERRORS["doc_stride"])
+    return Options(top_k, ma, mq, margin, nulls, stride)
 
 
 def check_pairs(payload: Dict[str, Any]) -> Tuple[List[str], List[List[str]]]:
@@ -109,6 +120,8 @@ def check_model(h, opt: Options) -> None:
         raise ValueError(ERRORS["max_query_tokens"])
     if opt.max_answer_tokens > S - 3:
         raise ValueError(ERRORS["max_answer_tokens"])
+    if opt.doc_stride is not None and opt.doc_stride > S - 3:
+        raise ValueError(WINDOW_ERRORS["doc_stride"])
 
 
 def result(h, opt: Options, questions: List[str], groups: List[List[str]], answers: List[List[Dict[str, Any]]],
@@ -142,7 +155,7 @@ def result(h, opt: Options, questions: List[str], groups: List[List[str]], answe
 
 
 def answer_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional[List[Any]]:
-    """The jobs of one lease that share (model, max_query_tokens, max_answer_tokens) as one engine call
+    """The jobs of one lease that share (model, max_query_tokens, max_answer_tokens, doc_stride) as one engine call
     (every rank calls it; a single job is a batch of one): their pairs concatenated, split contiguously
     over the DP ranks, the span / score / null rows all-gathered, ranked on rank 0 at the largest
     ``top_k``. A prefix of a total order is the smaller top-k, both among a pair's spans and among a
@@ -176,19 +189,27 @@ def answer_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
             # this rank's rows of every group; a question with none of them here costs nothing
             local = [min(max(g - s_r, 0), n_r) for g in goff]
             rows = h.engine.span_pairs(questions, passages[s_r:s_r + n_r], local, k, key.max_answer_tokens,
-                                       key.max_query_tokens)
+                                       key.max_query_tokens, key.doc_stride)
+            if key.doc_stride is not None:  # every pair's window count travels with its rows
+                rows = tuple(rows) + (h.engine.window_counts,)
         except Exception as e:
             exc = e
         counts = exchange_errors(exc, int(rows[0].shape[0]) if rows is not None else 0)
-        span, score, null = all_gather_rows(*rows, counts=counts)
+        span, score, null, *wcount = all_gather_rows(*rows, counts=counts)
         if rank == 0:
-            res = h.engine.rank_spans(span, score, null, passages, goff, k)
+            # windowed spans are tokens of the whole passage (cut at max_row_bytes), not of one row
+            res = h.engine.rank_spans(span, score, null, passages, goff, k,
+                                      token_cap=None if key.doc_stride is None else h.engine.max_row_bytes)
+            wcount = wcount[0].tolist() if wcount else None
             q0 = 0
             for i, opt, qs, gs in jobs:
                 try:
+                    extra: Dict[str, Any] = {"dp_world_size": ws} if ws > 1 else {}
+                    if wcount is not None:
+                        extra.update(doc_stride=opt.doc_stride,
+                                     window_count=int(sum(wcount[goff[q0]:goff[q0 + len(qs)]])))
                     out[i] = ("ok", result(h, opt, qs, gs, res.answers[q0:q0 + len(qs)],
-                                           res.null[goff[q0]:goff[q0 + len(qs)]], payloads[i],
-                                           {"dp_world_size": ws} if ws > 1 else {}))
+                                           res.null[goff[q0]:goff[q0 + len(qs)]], payloads[i], extra))
                 except Exception as e:
                     out[i] = ("err", e)
                 q0 += len(qs)
@@ -197,7 +218,7 @@ def answer_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
 
 @register_batch_op("map_answer")
 def map_answer_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
-    """Batch handler: jobs that share (model_path, max_query_tokens, max_answer_tokens) go to the device
+    """Batch handler: jobs that share (model_path, max_query_tokens, max_answer_tokens, doc_stride) go to the device
     together; malformed payloads take the single-job path and fail alone."""
     from agent_tpu_amd.parallel.dp_ops import dispatch
 
@@ -209,7 +230,8 @@ def map_answer_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
         try:
             opt = options(p)
             check_pairs(p)
-            groups.setdefault((p.get("model_path"), opt.max_query_tokens, opt.max_answer_tokens), []).append(i)
+            groups.setdefault((p.get("model_path"), opt.max_query_tokens, opt.max_answer_tokens, opt.doc_stride),
+                              []).append(i)
         except Exception:
             try:
                 out[i] = ("ok", run(p))
