@@ -451,6 +451,31 @@ PYBIND11_MODULE(_atpu, m) {
                        P<int32_t>(ent), P<float>(ent_sum), P<int32_t>(count), P<int32_t>(label_out),
                        P<float>(prob_out), P<float>(logits_out), B, Sq, H, L, V, mode, E, S(stream));
         });
+  m.def("fill_assemble",
+        [](uintptr_t ids_s, uintptr_t lens_s, uintptr_t segoff, uintptr_t ids, uintptr_t lens, uintptr_t pos, int B,
+           int Ns, int Sq, int M, int cls, int sep, int pad, int mask, uintptr_t stream) {
+          fill_assemble(P<const int32_t>(ids_s), P<const int32_t>(lens_s), P<const int32_t>(segoff), P<int32_t>(ids),
+                        P<int32_t>(lens), P<int32_t>(pos), B, Ns, Sq, M, cls, sep, pad, mask, S(stream));
+        });
+  m.def("mask_gather",
+        [](uintptr_t x, uintptr_t fin, uintptr_t gamma, uintptr_t beta, uintptr_t pos, uintptr_t mrow, uintptr_t mord,
+           uintptr_t xm, uintptr_t valid, int R, int B, int Sq, int M, int H, uintptr_t stream) {
+          mask_gather(P<const bf16>(x), P<const float>(fin), P<const float>(gamma), P<const float>(beta),
+                      P<const int32_t>(pos), P<const int32_t>(mrow), P<const int32_t>(mord), P<bf16>(xm),
+                      P<int32_t>(valid), R, B, Sq, M, H, S(stream));
+        });
+  m.def("vocab_topk_splits", &vocab_topk_splits, "the split count of vocab_topk for V tokens (a function of V alone)",
+        py::arg("V"));
+  m.def("vocab_topk_partial", [](uintptr_t t, uintptr_t E, uintptr_t bias, uintptr_t ws, uintptr_t logits_out, int R,
+                                 int V, int H, int k, uintptr_t stream) {
+    vocab_topk_partial(P<const float>(t), P<const bf16>(E), P<const float>(bias), P<float>(ws), P<float>(logits_out),
+                       R, V, H, k, S(stream));
+  });
+  m.def("vocab_topk_merge", [](uintptr_t ws, uintptr_t valid, uintptr_t lse_in, uintptr_t tok, uintptr_t logit,
+                               uintptr_t prob, uintptr_t lse, int R, int V, int k, uintptr_t stream) {
+    vocab_topk_merge(P<const float>(ws), P<const int32_t>(valid), P<const float>(lse_in), P<int32_t>(tok),
+                     P<float>(logit), P<float>(prob), P<float>(lse), R, V, k, S(stream));
+  });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

@@ -384,6 +384,42 @@ void tag_entities(const bf16* x, const float* fin, const float* u, const float* 
                   float* prob_out, float* logits_out, int B, int S, int H, int L, int V, int mode, int E,
                   hipStream_t stream);
 
+// ------------------------------------------- masked-token prediction (fill.hip, mlm_head.hip)
+// Mask rows "atpu-fill v1" (agent_tpu_amd/tokenizer.py fill_rows is the twin) from the single-segment
+// rows ids_s [Ns, S] / lens_s [Ns] of the pieces between a text's mask tokens; the pieces of row b are
+// segoff[b] .. segoff[b+1]-1 (segoff [B+1] clamped into [0, Ns], at most M + 1 of them are used):
+// [CLS] seg_0 [MASK] seg_1 ... seg_m [SEP] [PAD]..., the concatenation cut to its first S - 2 tokens;
+// lens = kept + 2; pos [B, M] = the row position of mask j, -1 where the row has fewer masks or the
+// mask fell at or beyond position S - 1. S >= 3, M in [1, 16]; B == 0: no launch; nothing outside the
+// given rows is touched.
+void fill_assemble(const int32_t* ids_s, const int32_t* lens_s, const int32_t* segoff, int32_t* ids, int32_t* lens,
+                   int32_t* pos, int B, int Ns, int S, int M, int cls, int sep, int pad, int mask, hipStream_t stream);
+// xm [R, H] bf16 = the encoder row x[mrow[r] * S + pos[mrow[r], mord[r]]] of mask slot r (x [B*S, H],
+// pos [B, M]). With fin [B*S, 2] = (rstd, rstd*mu) the rows are raw and the last LayerNorm is applied
+// here: (x * rstd - rstd mu) * gamma + beta in fp32, rounded once; without it the rows are copied.
+// A slot with mrow outside [0, B), mord outside [0, M) or pos outside [0, S) reads a clamped row,
+// writes zeros and valid[r] = 0 (else 1). H % 64 == 0 in [64, 1024]; R == 0: no launch.
+void mask_gather(const bf16* x, const float* fin, const float* gamma, const float* beta, const int32_t* pos,
+                 const int32_t* mrow, const int32_t* mord, bf16* xm, int32_t* valid, int R, int B, int S, int M, int H,
+                 hipStream_t stream);
+// logit[r, v] = t[r] . E[v] + bias[v] (t [R, H] fp32, E [V, H] bf16 widened exactly, one fp32
+// accumulator per (r, v) on the f32 MFMA, the k order a function of H alone, the bias added once
+// after the chain), its log-sum-exp over all V tokens and its top k in the order (logit desc, token
+// asc; a NaN ranks and returns as -inf and adds 0 to the sum). vocab_topk_partial fills the
+// workspace ws [R * P * (k + 1), 2] fp32 (the [R, P, k] list entries, then the [R, P] (max, sum) pairs) with
+// P = vocab_topk_splits(V) (a function of V alone: all four outputs of a
+// slot have the same bits whatever R and the slot's place; mlm_head.hip's header); logits_out [R, V]
+// optional (null: not written). vocab_topk_merge reduces them to tok [R, k] (-1 past V), logit [R, k]
+// (-inf), prob [R, k] = exp(logit - lse) (0) and lse [R]; with lse_in [R] prob uses it instead of the
+// launch's own; a slot with valid[r] == 0 (valid optional) returns (-1, -inf, 0) and lse = 0.
+// H % 64 == 0 in [64, 1024], V >= 1, k in [1, 32]; R == 0: no launch. Nothing outside E[0:V] and
+// bias[0:V] is read.
+int vocab_topk_splits(int V);
+void vocab_topk_partial(const float* t, const bf16* E, const float* bias, float* ws, float* logits_out, int R, int V,
+                        int H, int k, hipStream_t stream);
+void vocab_topk_merge(const float* ws, const int32_t* valid, const float* lse_in, int32_t* tok, float* logit,
+                      float* prob, float* lse, int R, int V, int k, hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

@@ -42,6 +42,7 @@ class BertConfig:
     eps: float = 1e-12
     qa_head: bool = False  # a span head (HF BertForQuestionAnswering qa_outputs) after the classifier
     tag_labels: int = 0  # > 0: a token classification head of that many labels after the other heads
+    mlm_head: bool = False  # a masked-LM head (HF BertForMaskedLM cls.predictions, decoder tied to emb.word) last
 
     @property
     def head_dim(self) -> int:
@@ -56,6 +57,8 @@ class BertConfig:
             head += 2 * H + 2
         if self.tag_labels > 0:
             head += self.tag_labels * H + self.tag_labels
+        if self.mlm_head:
+            head += H * H + 3 * H + self.vocab_size
         return emb + L * layer + head
 
     def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True,
@@ -133,6 +136,12 @@ def param_specs(cfg: BertConfig):
     if cfg.tag_labels > 0:
         yield "tag_w", (cfg.tag_labels, H), bf
         yield "tag_b", (cfg.tag_labels,), f32
+    if cfg.mlm_head:  # the decoder weight is emb.word (tied): no second [V, H] tensor
+        yield "mlm_w", (H, H), bf
+        yield "mlm_b", (H,), f32
+        yield "mlm_ln_g", (H,), f32
+        yield "mlm_ln_b", (H,), f32
+        yield "mlm_out_b", (cfg.vocab_size,), f32
 
 
 def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: float = 0.0,
@@ -164,9 +173,13 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor], head: str =
     ``BertForQuestionAnswering`` one (``qa_outputs``; no pooler, no classifier; ``cfg.qa_head``), or from
     a plain ``BertModel`` one (no ``bert.`` prefix, no classifier, the pooler optional): head
     tensors the dict does not have stay zero. ``head="token"``: a ``BertForTokenClassification`` dict
-    (no pooler), whose ``classifier.*`` is the tag head (``cfg.tag_labels``), not the row classifier."""
-    if head not in ("sequence", "token"):
-        raise ValueError("head must be 'sequence' or 'token'")
+    (no pooler), whose ``classifier.*`` is the tag head (``cfg.tag_labels``), not the row classifier.
+    ``head="mlm"``: a ``BertForMaskedLM`` dict (``cls.predictions.*``; ``cfg.mlm_head``); its decoder must be
+    tied to the word embeddings."""
+    if head not in ("sequence", "token", "mlm"):
+        raise ValueError("head must be 'sequence', 'token' or 'mlm'")
+    if head == "mlm" and not cfg.mlm_head:
+        raise ValueError("head 'mlm' needs a config with mlm_head")
     pack = ParamPack(param_specs(cfg))
     if "embeddings.word_embeddings.weight" in sd and "bert.embeddings.word_embeddings.weight" not in sd:
         sd = {"bert." + k: v for k, v in sd.items()}
@@ -200,6 +213,16 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor], head: str =
                       ("qa_w", "qa_outputs.weight"), ("qa_b", "qa_outputs.bias")):
         if key in sd and name in pack:
             put(name, sd[key])
+    if head == "mlm":
+        dec = sd.get("cls.predictions.decoder.weight")
+        if dec is not None and not torch.equal(dec, sd["bert.embeddings.word_embeddings.weight"]):
+            raise ValueError("untied MLM decoder: cls.predictions.decoder.weight differs from the word embeddings")
+        c = "cls.predictions."
+        put("mlm_w", sd[c + "transform.dense.weight"])
+        put("mlm_b", sd[c + "transform.dense.bias"])
+        put("mlm_ln_g", sd[c + "transform.LayerNorm.weight"])
+        put("mlm_ln_b", sd[c + "transform.LayerNorm.bias"])
+        put("mlm_out_b", sd[c + "bias"])
     return pack
 
 
@@ -275,6 +298,11 @@ class BertClassifier:
         # runs the same kernel on the normalised rows
         self.tag_fused = os.getenv("ATPU_TAG_FUSED", "1") not in ("0", "false", "no")
         self._tag_inputs: Optional[Dict[str, torch.Tensor]] = None
+        # mask predictions on the folded encoder: the last LayerNorm applied to the gathered mask
+        # rows only by mask_gather (ops/fill.py); ATPU_FILL_FUSED=0 finishes every row with
+        # ops.layernorm and gathers the normalised rows
+        self.fill_fused = os.getenv("ATPU_FILL_FUSED", "1") not in ("0", "false", "no")
+        self._fill_inputs: Optional[Dict[str, torch.Tensor]] = None
 
     # ------------------------------------------------------------ LN folding
     def folded(self) -> Dict[str, torch.Tensor]:
@@ -616,6 +644,62 @@ class BertClassifier:
         h = self.encode(ids, lens, type_ids, cls_only_last=False)
         return ops.tag_entities(h, lens, B, S, ti["w"], None, ti["b"], label_type, label_begin, mode, max_entities,
                                 ids=ids, cont=cont, **outs)
+
+    # ------------------------------------------------------------ masked-token prediction
+    def fill_inputs(self) -> Dict[str, torch.Tensor]:
+        """The MLM head as :meth:`fills` takes it (built once, on the device; build it outside graph
+        capture): ``E`` = ``emb.word`` (the tied decoder), ``bias`` = ``mlm_out_b`` and the last layer's
+        ``gamma`` / ``beta``."""
+        if not self.cfg.mlm_head:
+            raise ValueError("model has no MLM head")
+        if self._fill_inputs is None:
+            p = self.p
+            ln2 = f"l{self.cfg.layers - 1}."
+            self._fill_inputs = {"E": p["emb.word"].contiguous(), "bias": p["mlm_out_b"].float().contiguous(),
+                                 "gamma": p[ln2 + "ln2_g"].float().contiguous(),
+                                 "beta": p[ln2 + "ln2_b"].float().contiguous()}
+        return self._fill_inputs
+
+    def fill_transform(self, xm: torch.Tensor) -> torch.Tensor:
+        """The MLM transform of the gathered rows ``xm [R, H]`` -> ``t [R, H]`` fp32: dense + bias + erf-GELU,
+        then the LayerNorm ``mlm_ln_*``. The LayerNorm's output has the rows' dtype (bf16 on the GPU) and is
+        widened to fp32 for ``vocab_topk``; the fp32 CPU oracle keeps fp32 throughout."""
+        p = self.p
+        if xm.shape[0] == 0:
+            return torch.zeros(xm.shape, dtype=torch.float32, device=xm.device)
+        h = ops.linear(xm, p["mlm_w"], p["mlm_b"], act="gelu")
+        return ops.layernorm(h, p["mlm_ln_g"], p["mlm_ln_b"], self.cfg.eps).float()
+
+    def fills(self, ids: torch.Tensor, lens: torch.Tensor, pos: torch.Tensor, mrow: torch.Tensor,
+              mord: torch.Tensor, k: int, type_ids: Optional[torch.Tensor] = None,
+              tids: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Mask predictions of fill rows (``ops.fill_assemble``): ``(tok [R, k] int32, logit [R, k], prob [R, k],
+        lse [R])`` of :func:`ops.vocab_topk` for the mask slots ``mrow [R]`` / ``mord [R]`` (slot ``r`` is mask
+        ``mord[r]`` of row ``mrow[r]``, at ``pos [B, M]``). ``tids [T]`` int64 (``T <= 32``, distinct, in the
+        vocabulary): score only those tokens (HF's ``targets``): the same kernel over the gathered table
+        with the full vocabulary's ``lse``, ``tok`` mapped back through ``tids``, ``k`` capped at ``T``.
+        ``logits_out [R, V]`` fp32, when given, receives the full logits.
+
+        Every layer runs in full. On the folded encoder the final LayerNorm is not run over the rows but
+        applied to the gathered mask rows (``mask_gather`` with ``fin``)."""
+        B, S = ids.shape
+        fi = self.fill_inputs()
+        if ids.is_cuda and self.fill_fused and self.can_fold(B, S):
+            g, fin, _ = self.encode_folded(ids, lens, type_ids, raw=True)
+            xm, valid = ops.mask_gather(g, pos, mrow, mord, B, S, fin=fin, gamma=fi["gamma"], beta=fi["beta"])
+        else:
+            h = self.encode(ids, lens, type_ids, cls_only_last=False)
+            xm, valid = ops.mask_gather(h, pos, mrow, mord, B, S)
+        t = self.fill_transform(xm)
+        if tids is None:
+            return ops.vocab_topk(t, fi["E"], fi["bias"], k, valid=valid, logits_out=logits_out)
+        full = ops.vocab_topk(t, fi["E"], fi["bias"], 1, valid=valid, logits_out=logits_out)
+        kk = min(k, int(tids.numel()))
+        tok, logit, prob, _ = ops.vocab_topk(t, fi["E"][tids].contiguous(), fi["bias"][tids].contiguous(), kk,
+                                             valid=valid, lse_in=full[3])
+        back = tids.to(torch.int32)[tok.clamp(min=0).long()]
+        return torch.where(tok >= 0, back, tok), logit, prob, full[3]
 
     def head(self, h: torch.Tensor, B: int, S: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Pooler + classifier + softmax/top-k (K7) over encoder states ``h``."""

@@ -27,5 +27,7 @@ from .span import span_topk, span_topk_ok, span_topk_ref, span_logits_ref, span_
 from .window import window_assemble, window_assemble_ref, window_best, window_best_ref  # noqa: F401
 from .tag import (tag_entities, tag_ok, tag_logits_ref, tag_select_ref, tag_group_ref, tag_tables,  # noqa: F401
                   default_tag_names)
+from .fill import (fill_assemble, fill_assemble_ref, mask_gather, mask_gather_ref, vocab_topk, vocab_topk_ok,  # noqa: F401
+                   vocab_logits_ref, vocab_select_ref, vocab_topk_splits)
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

@@ -663,6 +663,39 @@ def tag_batch_task(payload: Dict[str, Any]) -> Any:
     return mt.tag_batch(h, payloads, rank, ws)
 
 
+# ------------------------------------------------------------------ map_fill
+@dp_task("map_fill")
+def fill_task(payload: Dict[str, Any]) -> Any:
+    """One map_fill job: the texts split contiguously over the ranks, each rank predicting the masks of its
+    slice, the per-text tok / prob / pos rows all-gathered (C2) after the error exchange and mapped to
+    candidates on rank 0 (:func:`ops.map_fill.fill_batch` with one job)."""
+    from ops import map_fill as mf
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    h = get_gpu_handle(get_model_path(payload.get("model_path")))
+    res = mf.fill_batch(h, [payload], rank, ws)
+    if rank != 0:
+        return None
+    kind, value = res[0]
+    if kind == "err":
+        raise value
+    return value
+
+
+@dp_task("map_fill_batch")
+def fill_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several map_fill jobs of one lease (same model, top_k, mask_token and targets): one collective
+    model load, then :func:`ops.map_fill.fill_batch` on every rank."""
+    from ops import map_fill as mf
+    from ops._gpu_runtime import get_gpu_handle, get_model_path
+
+    rank, ws = world()
+    payloads = payload["payloads"]
+    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+    return mf.fill_batch(h, payloads, rank, ws)
+
+
 # ---------------------------------------------------------- risk_accumulate
 def _local_values(payload: Dict[str, Any], rank: int, ws: int) -> Tuple[torch.Tensor, int]:
     """This rank's slice of a ``values`` / ``items`` payload, as fp64 (CSV payloads stream

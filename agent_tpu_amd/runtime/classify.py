@@ -30,8 +30,8 @@ from .. import ops
 from .._native import native
 from ..models.bert import BertClassifier, BertConfig
 from ..models.params import ParamPack
-from ..tokenizer import (CLS_ID, DEFAULT_MAX_ROW_BYTES, PAD_ID, SEP_ID, WordPieceVocab, default_max_query_tokens,
-                         pack_rows, token_spans, window_table)
+from ..tokenizer import (CLS_ID, DEFAULT_MAX_ROW_BYTES, MASK_ID, MAX_MASKS, PAD_ID, SEP_ID, WordPieceVocab,
+                         default_max_query_tokens, pack_rows, split_masks, token_spans, window_table)
 from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
@@ -83,6 +83,19 @@ class TagResult:
     truncated: List[int]     # the rows whose count exceeded max_entities
     ent: torch.Tensor        # [rows, E, 4] int32 (host): (first, last, type, n), (-1, -1, -1, 0) past the last
     ent_sum: torch.Tensor    # [rows, E] fp32 (host)
+
+
+@dataclass
+class FillResult:
+    rows: int
+    # per row, one record per mask in text order: {"start", "end": character offsets of the literal mask
+    # token in the row's text, "candidates": [{"token_id", "token": the vocabulary string (None for the hash
+    # tokenizer), "score": the probability}], best first}; a truncated mask has no candidates
+    fills: List[List[Dict[str, object]]]
+    truncated: List[Tuple[int, int]]  # the (row, mask) pairs that fell beyond the row
+    tok: torch.Tensor    # [rows, M, k] int32 (host): -1 past a row's masks, for a truncated mask, past the targets
+    prob: torch.Tensor   # [rows, M, k] fp32 (host)
+    pos: torch.Tensor    # [rows, M] int32 (host): the row position of every mask, -1 as tok
 
 
 @dataclass
@@ -1217,6 +1230,209 @@ class ClassifyEngine:
         """:meth:`tag_rows`, then :meth:`map_tags`: the entities of an in-memory list of strings."""
         ent, ent_sum, count = self.tag_rows(rows, mode, max_entities)
         return self.map_tags(ent, ent_sum, count, rows, mode)
+
+    # ------------------------------------------------------------ masked-token prediction (map_fill)
+    # The staging of embed_texts with the text split at its mask tokens on the host: per chunk of at most B
+    # texts one H2D of the packed pieces, their offsets and the compact slot lists (the host knows every
+    # text's mask count), one captured graph per ("fill", row bucket, slot bucket, k, targets) (tokenize the
+    # pieces, fill_assemble, model.fills) and D2D scatters of the slots into per-text [N, M, k] buffers; one
+    # D2H per call. The slot count is padded to 16 * 2^i with invalid slots.
+    FILL_NO_HEAD = "model has no MLM head"
+    FILL_NO_MASK_ID = "vocabulary has no [MASK] token"
+    FILL_TOO_MANY = "a text has more than 16 mask tokens"
+
+    def _mask_id(self) -> int:
+        if self.vocab is None:
+            return MASK_ID
+        if self.vocab.mask_id is None:
+            raise ValueError(self.FILL_NO_MASK_ID)
+        return int(self.vocab.mask_id)
+
+    def _fill_bufs(self) -> Dict[str, torch.Tensor]:
+        """The fill buffers, allocated once on first use (captured graphs keep their addresses): token rows and
+        offsets for up to 17 B pieces, the rows' segment offsets, the mask positions and the slot lists."""
+        if getattr(self, "_fl", None) is None:
+            dev, B, S = self.device, self.B, self.S
+            segcap, rcap = (MAX_MASKS + 1) * B, MAX_MASKS * B
+
+            def i32(*shape, **kw):
+                return torch.zeros(shape, dtype=torch.int32, **kw)
+
+            fl = {"offs": i32(segcap + 1, device=dev), "ids_s": i32(segcap, S, device=dev),
+                  "lens_s": i32(segcap, device=dev), "segoff": i32(B + 1, device=dev), "ids": i32(B, S, device=dev),
+                  "lens": i32(B, device=dev), "pos": i32(B, MAX_MASKS, device=dev), "mrow": i32(rcap, device=dev),
+                  "mord": i32(rcap, device=dev), "tids": torch.zeros(ops.fill.MAX_K, dtype=torch.int64, device=dev)}
+            if dev.type == "cuda":
+                fl.update(pin_offs=i32(segcap + 1, pin_memory=True), pin_segoff=i32(B + 1, pin_memory=True),
+                          pin_mrow=i32(rcap, pin_memory=True), pin_mord=i32(rcap, pin_memory=True))
+            self._fl = fl
+        return self._fl
+
+    def _fill_step(self, bucket: int, segs: int, slots: int, k: int, T: int):
+        f = self._fl
+        cls_id, sep_id, pad_id = self._special_ids()
+        self._tokenize(self.text[0], f["offs"], ids=f["ids_s"], lens=f["lens_s"], rows=segs)
+        ops.fill_assemble(f["ids_s"][:segs], f["lens_s"][:segs], f["segoff"], MAX_MASKS, cls_id, sep_id, pad_id,
+                          self._mask_id(), ids=f["ids"], lens=f["lens"], pos=f["pos"], rows=bucket)
+        tok, _, prob, _ = self.model.fills(f["ids"][:bucket], f["lens"][:bucket], f["pos"][:bucket], f["mrow"][:slots],
+                                           f["mord"][:slots], k, tids=f["tids"][:T] if T else None)
+        return tok, prob, f["pos"]
+
+    def _fill_bucket(self, bucket: int, segs: int, slots: int, k: int, T: int):
+        if not self.use_graph:
+            return self._fill_step(bucket, segs, slots, k, T)
+        gk = ("fill", bucket, segs, slots, k, T)
+        if gk not in self._bgraphs:
+            self.model.fill_inputs()  # built here, not inside the capture
+            self._warm(lambda: self._fill_step(bucket, segs, slots, k, T))
+            self._bgraphs[gk] = capture_graph(lambda: self._fill_step(bucket, segs, slots, k, T), pool=self._bpool)
+        g, out = self._bgraphs[gk]
+        g.replay()
+        return out
+
+    def _slot_bucket(self, R: int) -> int:
+        b = 16
+        while b < R:
+            b *= 2
+        return min(b, MAX_MASKS * self.B)  # the slot buffers' size (R never exceeds it)
+
+    def _check_fill_args(self, top_k, mask_token, tids) -> Tuple[int, Optional[List[int]]]:
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.fill.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        if not isinstance(mask_token, str) or not mask_token:
+            raise ValueError("mask_token must be a non-empty string")
+        if not self.cfg.mlm_head:
+            raise ValueError(self.FILL_NO_HEAD)
+        self._mask_id()
+        if tids is not None:
+            tids = [int(t) for t in tids]
+            if not 1 <= len(tids) <= ops.fill.MAX_K or len(set(tids)) != len(tids) or any(
+                    not 0 <= t < self.cfg.vocab_size for t in tids):
+                raise ValueError("targets must be 1 to 32 distinct token ids of the vocabulary")
+        return top_k, tids
+
+    def fill_rows(self, rows: Sequence[str], top_k: int = 5, mask_token: str = "[MASK]",
+                  tids: Optional[Sequence[int]] = None, max_masks: Optional[int] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The mask predictions of every text: ``(tok [N, M, k] int32, prob [N, M, k] fp32, pos [N, M] int32)``
+        left on the engine's device (a DP caller all-gathers them), ``M`` = ``max_masks`` (default: the largest
+        mask count of ``rows``, at least 1), ``k = min(top_k, len(tids))`` with targets. Slots past a text's
+        masks are ``(-1, 0, -1)``. The pieces of a text are cut to ``max_row_bytes`` bytes in total, in text order
+        (the mask tokens do not count): the cut depends on the text alone, and a chunk always fits the text slot.
+        Masks after the cut follow the cut text directly."""
+        k, tids = self._check_fill_args(top_k, mask_token, tids)
+        if self.S < 3:
+            raise ValueError("fill_texts needs seq_len >= 3")
+        T = len(tids) if tids is not None else 0
+        kk = min(k, T) if T else k
+        split = [split_masks(r if isinstance(r, str) else bytes(r).decode("utf-8"), mask_token)[0] for r in rows]
+        counts = [len(p) - 1 for p in split]
+        if counts and max(counts) > MAX_MASKS:
+            raise ValueError(self.FILL_TOO_MANY)
+        M = max([1] + counts) if max_masks is None else int(max_masks)
+        if not max([1] + counts) <= M <= MAX_MASKS:
+            raise ValueError("max_masks must cover every text's masks and be at most 16")
+        N, dev = len(rows), self.device
+        tok = torch.full((N, M, kk), -1, dtype=torch.int32, device=dev)
+        prob = torch.zeros((N, M, kk), dtype=torch.float32, device=dev)
+        pos = torch.full((N, M), -1, dtype=torch.int32, device=dev)
+        f = self._fill_bufs()
+        if T:
+            f["tids"][:T].copy_(torch.tensor(tids, dtype=torch.int64))
+        for b0 in range(0, N, self.B):
+            parts = split[b0:b0 + self.B]
+            n = len(parts)
+            pieces: List[bytes] = []
+            for ps in parts:  # per text: max_row_bytes in all, so B texts fit the B * max_row_bytes text slot
+                budget = self.max_row_bytes
+                for p in ps:
+                    pieces.append(p.encode("utf-8")[:budget])
+                    budget -= len(pieces[-1])
+            text, offs = pack_rows(pieces)
+            segoff = np.zeros(n + 1, dtype=np.int32)
+            segoff[1:] = np.cumsum([len(ps) for ps in parts])
+            mrow = np.array([i for i, ps in enumerate(parts) for _ in range(len(ps) - 1)], dtype=np.int32)
+            mord = np.array([j for ps in parts for j in range(len(ps) - 1)], dtype=np.int32)
+            R = int(mrow.size)
+            if dev.type == "cuda":
+                pin = self._pinned()
+                bk = self._bucket(n)
+                segs = 2 * bk if len(pieces) <= 2 * bk else (MAX_MASKS + 1) * bk
+                Rb = self._slot_bucket(R)
+                pin["text"][:text.size].copy_(torch.from_numpy(text))
+                f["pin_offs"][:len(pieces) + 1].copy_(torch.from_numpy(offs))
+                f["pin_offs"][len(pieces) + 1:segs + 1].fill_(int(offs[-1]))  # padding pieces: empty strings
+                f["pin_segoff"][:n + 1].copy_(torch.from_numpy(segoff))
+                f["pin_segoff"][n + 1:bk + 1].fill_(int(segoff[-1]))  # padding rows: no pieces, [CLS] [SEP]
+                f["pin_mrow"][:R].copy_(torch.from_numpy(mrow))
+                f["pin_mrow"][R:Rb].fill_(-1)  # padding slots: invalid
+                f["pin_mord"][:R].copy_(torch.from_numpy(mord))
+                f["pin_mord"][R:Rb].fill_(0)
+                if text.size:
+                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
+                f["offs"][:segs + 1].copy_(f["pin_offs"][:segs + 1], non_blocking=True)
+                f["segoff"][:bk + 1].copy_(f["pin_segoff"][:bk + 1], non_blocking=True)
+                f["mrow"][:Rb].copy_(f["pin_mrow"][:Rb], non_blocking=True)
+                f["mord"][:Rb].copy_(f["pin_mord"][:Rb], non_blocking=True)
+                t_, p_, ps_ = self._fill_bucket(bk, segs, Rb, k, T)
+                if R:
+                    dst = (f["mrow"][:R].long() + b0) * M + f["mord"][:R].long()
+                    tok.view(N * M, kk).index_copy_(0, dst, t_[:R])
+                    prob.view(N * M, kk).index_copy_(0, dst, p_[:R])
+                pos[b0:b0 + n].copy_(ps_[:n, :M])
+                torch.cuda.current_stream(dev).synchronize()  # the pinned rows are free again
+            else:
+                cls_id, sep_id, pad_id = self._special_ids()
+                ids_s, lens_s = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
+                ids, lens, ps_ = ops.fill_assemble(ids_s, lens_s, torch.from_numpy(segoff), MAX_MASKS, cls_id, sep_id,
+                                                   pad_id, self._mask_id())
+                t_, _, p_, _ = self.model.fills(ids, lens, ps_, torch.from_numpy(mrow), torch.from_numpy(mord), k,
+                                                tids=f["tids"][:T] if T else None)
+                if R:
+                    dst = (torch.from_numpy(mrow).long() + b0) * M + torch.from_numpy(mord).long()
+                    tok.view(N * M, kk).index_copy_(0, dst, t_)
+                    prob.view(N * M, kk).index_copy_(0, dst, p_.float())
+                pos[b0:b0 + n].copy_(ps_[:, :M])
+        return tok, prob, pos
+
+    def map_fills(self, tok: torch.Tensor, prob: torch.Tensor, pos: torch.Tensor, rows: Sequence[str],
+                  mask_token: str = "[MASK]") -> "FillResult":
+        """Slots -> candidates on the host: one D2H, then every mask's candidates with the character offsets
+        of its literal mask token. A mask with ``pos == -1`` fell beyond the row: no candidates, listed in
+        ``truncated``."""
+        N, M, k = (int(v) for v in tok.shape)
+        if len(rows) != N:
+            raise ValueError("map_fills: one row of text per record row")
+        both = torch.cat([tok.view(torch.float32).reshape(-1), prob.reshape(-1),
+                          pos.view(torch.float32).reshape(-1)]).cpu()  # one D2H, one sync
+        tok_h = both[:N * M * k].clone().view(torch.int32).view(N, M, k)
+        prob_h = both[N * M * k:2 * N * M * k].clone().view(N, M, k)
+        pos_h = both[2 * N * M * k:].clone().view(torch.int32).view(N, M)
+        names = self.vocab.entries if self.vocab is not None else None
+        fills: List[List[Dict[str, object]]] = []
+        truncated: List[Tuple[int, int]] = []
+        for i in range(N):
+            r = rows[i]
+            spans = split_masks(r if isinstance(r, str) else bytes(r).decode("utf-8"), mask_token)[1]
+            row: List[Dict[str, object]] = []
+            for j, (a, b) in enumerate(spans):
+                cands: List[Dict[str, object]] = []
+                if pos_h[i, j] < 0:
+                    truncated.append((i, j))
+                else:
+                    for t, p in zip(tok_h[i, j].tolist(), prob_h[i, j].tolist()):
+                        if t >= 0:
+                            name = names[t].decode("utf-8", "replace") if names is not None and t < len(names) else None
+                            cands.append({"token_id": t, "token": name, "score": p})
+                row.append({"start": a, "end": b, "candidates": cands})
+            fills.append(row)
+        return FillResult(N, fills, truncated, tok_h, prob_h, pos_h)
+
+    def fill_texts(self, rows: Sequence[str], top_k: int = 5, mask_token: str = "[MASK]",
+                   tids: Optional[Sequence[int]] = None) -> "FillResult":
+        """:meth:`fill_rows`, then :meth:`map_fills`: the mask candidates of an in-memory list of strings."""
+        tok, prob, pos = self.fill_rows(rows, top_k, mask_token, tids)
+        return self.map_fills(tok, prob, pos, rows, mask_token)
 
     def rank_scores(self, scores: torch.Tensor, goff: Sequence[int], top_k: int = 10,
                     activation: str = "none") -> RerankResult:

@@ -58,6 +58,11 @@ the window geometry with the start positions each window owns (:func:`window_tab
 window rows (:func:`window_rows`; HIP kernel ``csrc/kernels/window.hip``, bit-for-bit). The spec is
 the docstrings of the two.
 
+atpu-fill v1 — rows with ``[MASK]`` tokens for masked-token prediction: the text is split at every
+literal mask token (:func:`split_masks`), the pieces are tokenized as ordinary rows and joined with
+the mask id between them (:func:`fill_rows`; HIP kernel ``csrc/kernels/fill.hip``, bit-for-bit). The
+spec is the docstring of :func:`fill_rows`.
+
 Token byte offsets — the tokenizers return ids only; :func:`token_spans` (hash) and
 :meth:`WordPieceVocab.token_spans` give, host side only, the ``(byte_start, byte_end)`` of every id
 that ``token_ids`` returns for the same row and cap: a hash piece or a matched WordPiece piece gets
@@ -197,6 +202,8 @@ class WordPieceVocab:
         if missing:
             raise ValueError(f"{source}: vocabulary has no {', '.join(missing)}")
         self.pad_id, self.unk_id, self.cls_id, self.sep_id = (index[s] for s in SPECIAL_TOKENS)
+        self.mask_id: Optional[int] = index.get(b"[MASK]")  # None: the vocabulary cannot fill masks
+        self.index = index
         self.max_len = max([1] + [len(p) for d in (self.first, self.cont) for p in d])
         self._table: Optional[np.ndarray] = None
         self._device: Dict[str, object] = {}
@@ -474,3 +481,75 @@ def window_rows(ids_q: np.ndarray, lens_q: np.ndarray, ids_p: np.ndarray, lens_p
         lens[r] = nq + nw + 3
         own[r] = (0 if a == 0 else h, nw if a + cap >= T else step + h)
     return ids, types, lens, own
+
+
+MASK_ID = 103  # [MASK] of the hash tokenizer (the id bert-base-uncased gives it)
+MAX_MASKS = 16
+
+
+def split_masks(text: str, mask_token: str = "[MASK]") -> Tuple[List[str], List[Tuple[int, int]]]:
+    """The pieces of ``text`` between the literal, case-sensitive occurrences of ``mask_token`` (``m + 1``
+    pieces for ``m`` masks, empty ones included) and the ``(start, end)`` character offsets of the masks."""
+    if not mask_token:
+        raise ValueError("mask_token must be a non-empty string")
+    pieces, spans, at = [], [], 0
+    while True:
+        i = text.find(mask_token, at)
+        if i < 0:
+            pieces.append(text[at:])
+            return pieces, spans
+        pieces.append(text[at:i])
+        spans.append((i, i + len(mask_token)))
+        at = i + len(mask_token)
+
+
+def fill_rows(ids_s: np.ndarray, lens_s: np.ndarray, segoff: np.ndarray, max_masks: int, cls_id: int = CLS_ID,
+              sep_id: int = SEP_ID, pad_id: int = PAD_ID, mask_id: int = MASK_ID
+              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """atpu-fill v1: rows with mask tokens; pure-Python twin of ``csrc/kernels/fill.hip``
+    ``fill_assemble_kernel``, bit-for-bit. Both tokenizers turn a literal ``[MASK]`` into punctuation plus
+    a word, so (as HF does) the host splits each text at every literal mask token (:func:`split_masks`)
+    and the pieces are tokenized as ordinary single-segment rows ``ids_s [Ns, S]`` / ``lens_s [Ns]``; the
+    pieces of row ``b`` are ``segoff[b] .. segoff[b + 1] - 1``. With ``a = clamp(segoff[b], 0, Ns)``,
+    ``nseg = clamp(clamp(segoff[b + 1], 0, Ns) - a, 0, M + 1)``, piece ``i`` the row ``min(a + i, Ns - 1)`` and
+    ``n_i = clamp(lens_s, 2, S) - 2`` its tokens without ``[CLS]`` / ``[SEP]``:
+
+    * the concatenation ``c = seg_0 [MASK] seg_1 [MASK] ... seg_{nseg-1}`` has ``T`` tokens, of which the
+      first ``kept = min(T, S - 2)`` stay;
+    * ``ids = [CLS] c[0:kept] [SEP]`` then ``[PAD]``; ``len = kept + 2``; every ``type_id`` is 0;
+    * ``pos[b, j]`` = the row position of mask ``j`` (``1 +`` its index in ``c``), or ``-1`` where the row has
+      fewer masks or the mask fell at or beyond position ``S - 1``.
+
+    ``S >= 3``, ``M = max_masks`` in ``[1, 16]``. Returns ``(ids [B, S], lens [B], pos [B, M])``, all int32."""
+    ids_s = np.asarray(ids_s, dtype=np.int32)
+    lens_s, segoff = np.asarray(lens_s, dtype=np.int32), np.asarray(segoff, dtype=np.int32)
+    M = int(max_masks)
+    if ids_s.ndim != 2 or lens_s.shape != (ids_s.shape[0],):
+        raise ValueError("fill_rows: ids_s [Ns, S] and lens_s [Ns]")
+    Ns, S = ids_s.shape
+    if S < 3 or not 1 <= M <= MAX_MASKS or segoff.ndim != 1 or segoff.shape[0] < 1:
+        raise ValueError("fill_rows: S >= 3, max_masks in [1, 16] and segoff [B + 1]")
+    B = segoff.shape[0] - 1
+    if B > 0 and Ns < 1:
+        raise ValueError("fill_rows: Ns >= 1")
+    ids = np.full((B, S), pad_id, dtype=np.int32)
+    lens = np.zeros(B, dtype=np.int32)
+    pos = np.full((B, M), -1, dtype=np.int32)
+    for b in range(B):
+        a = min(max(int(segoff[b]), 0), Ns)
+        nseg = min(max(min(max(int(segoff[b + 1]), 0), Ns) - a, 0), M + 1)
+        c: List[int] = []
+        for i in range(nseg):
+            s = min(a + i, Ns - 1)
+            n = min(max(int(lens_s[s]), 2), S) - 2
+            c.extend(int(t) for t in ids_s[s, 1:1 + n])
+            if i + 1 < nseg:
+                if len(c) < S - 2:
+                    pos[b, i] = len(c) + 1
+                c.append(mask_id)
+        kept = min(len(c), S - 2)
+        ids[b, 0] = cls_id
+        ids[b, 1:1 + kept] = c[:kept]
+        ids[b, 1 + kept] = sep_id
+        lens[b] = kept + 2
+    return ids, lens, pos

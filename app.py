@@ -246,9 +246,9 @@ METRICS = Metrics()
 
 
 # --------------------------------------------------------------- profile
-GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag",
+GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag", "map_fill",
            "map_summarize", "risk_accumulate"}
-BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag",
+BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag", "map_fill",
              "map_summarize"}
 
 

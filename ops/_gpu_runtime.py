@@ -26,6 +26,10 @@ random-init span head next to the pooler and classifier.
 tag head ``map_tag`` needs), the json names its labels in ``"tag_labels": [...]`` (``"outside": ["O"]`` by
 default), ``pool_*`` / ``cls_*`` are optional, and ``map_classify`` / ``map_rerank`` / ``map_answer`` refuse it.
 ``?tags=N`` on a preset adds a random-init tag head of ``N`` labels named ``O, B-T0, I-T0, B-T1, ...``.
+``"head": "mlm"`` marks a ``BertForMaskedLM`` export: the file holds ``mlm_w`` / ``mlm_b`` / ``mlm_ln_g`` /
+``mlm_ln_b`` / ``mlm_out_b`` (the masked-LM head ``map_fill`` needs; the decoder is the word embeddings),
+``pool_*`` / ``cls_*`` are optional, and the other head ops refuse it. ``?mlm=1`` on a preset adds a
+random-init MLM head.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -63,6 +67,7 @@ class ModelSpec:
     tags: int = 0  # labels of a tag head ("?tags=N", or "head": "token" in the json, which clears ``head``): map_tag
     tag_names: Optional[Tuple[str, ...]] = None  # "tag_labels" of the json; None: ops.default_tag_names
     tag_outside: Tuple[str, ...] = ("O",)
+    mlm: bool = False  # a masked-LM head ("?mlm=1", or "head": "mlm" in the json, which clears ``head``): map_fill
 
 
 def _flag(value: Any) -> bool:
@@ -93,7 +98,8 @@ def parse_spec(path: str) -> ModelSpec:
         return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
                          int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
                          vocab=vocab, lowercase=True if lowercase is None else lowercase,
-                         qa=_flag(q.get("qa", "0")), tags=_tags(q.get("tags", "0")))
+                         qa=_flag(q.get("qa", "0")), tags=_tags(q.get("tags", "0")),
+                         mlm=_flag(q.get("mlm", "0")))
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
@@ -114,8 +120,8 @@ def parse_spec(path: str) -> ModelSpec:
             outside = tuple(str(n) for n in meta.get("outside", ["O"]))
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
                          file=base, quant=quant, vocab=vocab, lowercase=lowercase,
-                         head=head not in ("none", "qa", "token"), qa=head == "qa",
-                         tags=len(names) if names else 0, tag_names=names, tag_outside=outside)
+                         head=head not in ("none", "qa", "token", "mlm"), qa=head == "qa",
+                         tags=len(names) if names else 0, tag_names=names, tag_outside=outside, mlm=head == "mlm")
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -204,7 +210,8 @@ def _build_handle(model_path: str, device) -> GpuHandle:
 
     def local():
         spec = parse_spec(model_path)
-        cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa, tag_labels=spec.tags)
+        cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa, tag_labels=spec.tags,
+                         mlm_head=spec.mlm)
         box.update(spec=spec, cfg=cfg)
         # the vocabulary is read and its table built on every rank (same file, same node: no
         # broadcast), before the weights, so a missing or bad file on any rank fails the load on all
