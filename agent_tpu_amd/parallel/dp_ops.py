@@ -16,11 +16,14 @@ Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
 ``risk_accumulate`` (C3 all-reduce of {count,sum,min,max}),
 ``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
 tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
-per-rank top-k lists, merged on rank 0) and the ``map_rerank`` tasks (C2
-all-gather of pair scores, ranked on rank 0).
+per-rank top-k lists, merged on rank 0) and, from the :data:`BATCHED_OPS`
+table, the ``map_rerank``, ``map_answer``, ``map_tag`` and ``map_fill`` tasks
+with their ``_batch`` forms (C2 all-gather of pair scores, span rows, entity
+records or mask candidates, ranked or mapped on rank 0).
 """
 from __future__ import annotations
 
+import importlib
 import os
 import threading
 import time
@@ -562,138 +565,42 @@ def search_batch_task(payload: Dict[str, Any]) -> Any:
     return ms.search_batch(payload["payloads"], rank, ws)
 
 
-# --------------------------------------------------------------- map_rerank
-@dp_task("map_rerank")
-def rerank_task(payload: Dict[str, Any]) -> Any:
-    """One map_rerank job: the pairs split contiguously over the ranks, each rank scoring its slice
-    with the queries it needs, the scores all-gathered (C2) after the error exchange and ranked on
-    rank 0 (:func:`ops.map_rerank.rerank_batch` with one job)."""
-    from ops import map_rerank as mr
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    h = get_gpu_handle(get_model_path(payload.get("model_path")))
-    res = mr.rerank_batch(h, [payload], rank, ws)
-    if rank != 0:
-        return None
-    kind, value = res[0]
-    if kind == "err":
-        raise value
-    return value
+# ------------------------------------------- map_rerank, map_answer, map_tag, map_fill
+#: task name -> (``ops`` module, its batch function); every op has a single-job task under its own name
+#: and a ``_batch`` task for the jobs of one lease that share its group key
+BATCHED_OPS = {"map_rerank": ("map_rerank", "rerank_batch"), "map_rerank_batch": ("map_rerank", "rerank_batch"),
+               "map_answer": ("map_answer", "answer_batch"), "map_answer_batch": ("map_answer", "answer_batch"),
+               "map_tag": ("map_tag", "tag_batch"), "map_tag_batch": ("map_tag", "tag_batch"),
+               "map_fill": ("map_fill", "fill_batch"), "map_fill_batch": ("map_fill", "fill_batch")}
 
 
-@dp_task("map_rerank_batch")
-def rerank_batch_task(payload: Dict[str, Any]) -> Any:
-    """Several map_rerank jobs of one lease (same model, max_query_tokens and label): one collective
-    model load, then :func:`ops.map_rerank.rerank_batch` on every rank."""
-    from ops import map_rerank as mr
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
+def _register_batched(name: str, module: str, batch_fn: str) -> None:
+    """Both task forms run the op's ``X_batch(h, payloads, rank, ws)`` on every rank after one collective
+    model load: the pairs or texts are split contiguously over the ranks, the per-rank rows all-gathered
+    (C2) after the error exchange and mapped on rank 0. A single job is a batch of one whose entry is
+    unwrapped, an ``"err"`` raised. The op module is imported here, in the task body: a worker rank
+    imports this module alone before its first task."""
+    single = not name.endswith("_batch")
 
-    rank, ws = world()
-    payloads = payload["payloads"]
-    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
-    return mr.rerank_batch(h, payloads, rank, ws)
+    @dp_task(name)
+    def task(payload: Dict[str, Any]) -> Any:
+        from ops._gpu_runtime import get_gpu_handle, get_model_path
 
-
-# --------------------------------------------------------------- map_answer
-@dp_task("map_answer")
-def answer_task(payload: Dict[str, Any]) -> Any:
-    """One map_answer job: the (question, passage) pairs split contiguously over the ranks, each rank
-    reading its slice, the per-pair span / score / null rows all-gathered (C2) after the error exchange
-    and ranked on rank 0 (:func:`ops.map_answer.answer_batch` with one job). With ``doc_stride`` each rank
-    reads its pairs' windows and folds them per pair before the gather, so the collective is unchanged but
-    for one ``[P]`` int32 row of window counts."""
-    from ops import map_answer as ma
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    h = get_gpu_handle(get_model_path(payload.get("model_path")))
-    res = ma.answer_batch(h, [payload], rank, ws)
-    if rank != 0:
-        return None
-    kind, value = res[0]
-    if kind == "err":
-        raise value
-    return value
+        run =getattr(importlib.import_module(f"ops.{module}"), batch_fn)
+        rank, ws = world()
+        payloads = [payload] if single else payload["payloads"]
+        h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
+        res = run(h, payloads, rank, ws)
+        if not single or rank != 0:
+            return res
+        kind, value = res[0]
+        if kind == "err":
+            raise value
+        return value
 
 
-@dp_task("map_answer_batch")
-def answer_batch_task(payload: Dict[str, Any]) -> Any:
-    """Several map_answer jobs of one lease (same model, max_query_tokens, max_answer_tokens and doc_stride): one
-    collective model load, then :func:`ops.map_answer.answer_batch` on every rank."""
-    from ops import map_answer as ma
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    payloads = payload["payloads"]
-    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
-    return ma.answer_batch(h, payloads, rank, ws)
-
-
-# ------------------------------------------------------------------ map_tag
-@dp_task("map_tag")
-def tag_task(payload: Dict[str, Any]) -> Any:
-    """One map_tag job: the texts split contiguously over the ranks, each rank tagging its slice, the
-    per-row ent / ent_sum / count records all-gathered (C2) after the error exchange and mapped to
-    character offsets on rank 0 (:func:`ops.map_tag.tag_batch` with one job)."""
-    from ops import map_tag as mt
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    h = get_gpu_handle(get_model_path(payload.get("model_path")))
-    res = mt.tag_batch(h, [payload], rank, ws)
-    if rank != 0:
-        return None
-    kind, value = res[0]
-    if kind == "err":
-        raise value
-    return value
-
-
-@dp_task("map_tag_batch")
-def tag_batch_task(payload: Dict[str, Any]) -> Any:
-    """Several map_tag jobs of one lease (same model, aggregation and max_entities): one collective
-    model load, then :func:`ops.map_tag.tag_batch` on every rank."""
-    from ops import map_tag as mt
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    payloads = payload["payloads"]
-    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
-    return mt.tag_batch(h, payloads, rank, ws)
-
-
-# ------------------------------------------------------------------ map_fill
-@dp_task("map_fill")
-def fill_task(payload: Dict[str, Any]) -> Any:
-    """One map_fill job: the texts split contiguously over the ranks, each rank predicting the masks of its
-    slice, the per-text tok / prob / pos rows all-gathered (C2) after the error exchange and mapped to
-    candidates on rank 0 (:func:`ops.map_fill.fill_batch` with one job)."""
-    from ops import map_fill as mf
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    h = get_gpu_handle(get_model_path(payload.get("model_path")))
-    res = mf.fill_batch(h, [payload], rank, ws)
-    if rank != 0:
-        return None
-    kind, value = res[0]
-    if kind == "err":
-        raise value
-    return value
-
-
-@dp_task("map_fill_batch")
-def fill_batch_task(payload: Dict[str, Any]) -> Any:
-    """Several map_fill jobs of one lease (same model, top_k, mask_token and targets): one collective
-    model load, then :func:`ops.map_fill.fill_batch` on every rank."""
-    from ops import map_fill as mf
-    from ops._gpu_runtime import get_gpu_handle, get_model_path
-
-    rank, ws = world()
-    payloads = payload["payloads"]
-    h = get_gpu_handle(get_model_path(payloads[0].get("model_path")))
-    return mf.fill_batch(h, payloads, rank, ws)
+for _name, (_module, _fn) in BATCHED_OPS.items():
+    _register_batched(_name, _module, _fn)
 
 
 # ---------------------------------------------------------- risk_accumulate

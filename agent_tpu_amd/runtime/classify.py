@@ -36,6 +36,10 @@ from ..utils.trace import DeviceStages, span
 from .graphs import capture_graph
 
 
+def i32(*shape, **kw) -> torch.Tensor:
+    return torch.zeros(shape, dtype=torch.int32, **kw)
+
+
 @dataclass
 class BatchResult:
     rows: int
@@ -175,6 +179,11 @@ class ClassifyEngine:
         # embeds allocates nothing for them), from the graph pools of the classify graphs
         self._egraphs: Dict[Tuple[int, str, bool], Tuple["torch.cuda.CUDAGraph", torch.Tensor]] = {}
         self._epools: Dict[int, Tuple[int, int]] = {}
+        # bucket graphs of the small-job forms (:meth:`_replay`), keyed by kind, bucket and whatever else
+        # the step was captured with; they replay in order on one stream, so one pool, made on first
+        # use, serves them all
+        self._bgraphs: Dict[tuple, Tuple["torch.cuda.CUDAGraph", object]] = {}
+        self._bpool: Optional[Tuple[int, int]] = None
 
     # ------------------------------------------------------------ device step
     def _tokenize(self, text: torch.Tensor, offs: torch.Tensor, ids: Optional[torch.Tensor] = None,
@@ -193,14 +202,17 @@ class ClassifyEngine:
         self._tokenize(self.text[slot], self.offs[slot], ids=ids, lens=lens, rows=rows)
         return self.model.forward(ids[:rows], lens[:rows], self.k)
 
+    def _warm(self, fn) -> None:
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):  # warm up allocator + code objects off-graph
+            fn()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+
     def _graph_step(self, slot: int):
         if slot not in self._graphs:
             if not self._graphs:  # once per engine: the other slots' steps take the same kernels
-                s = torch.cuda.Stream(self.device)
-                s.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(s):  # warm up allocator + code objects off-graph
-                    self._step(slot, self.B)
-                torch.cuda.current_stream(self.device).wait_stream(s)
+                self._warm(lambda: self._step(slot, self.B))
             g, outs = capture_graph(lambda: self._step(slot, self.B))
             self._graphs[slot] = (g, outs)
         g, outs = self._graphs[slot]
@@ -226,11 +238,7 @@ class ClassifyEngine:
     def _staged_graphs(self, slot: int):
         if slot not in self._staged:
             tok, enc, head = self._stage_fns(slot, self.B)
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):  # warm-up off-graph
-                tok(), enc(), head()
-            torch.cuda.current_stream(self.device).wait_stream(s)
+            self._warm(lambda: (tok(), enc(), head()))
             pool = torch.cuda.graph_pool_handle()
             gs = []
             outs = None
@@ -291,37 +299,60 @@ class ClassifyEngine:
                 "text": torch.zeros(self.B * self.max_row_bytes, dtype=torch.uint8, pin_memory=True),
                 "offs": torch.zeros(self.B + 1, dtype=torch.int32, pin_memory=True),
             }
-            self._bpool = torch.cuda.graph_pool_handle()
-            self._bgraphs = {}
         return self._pin
 
-    def _bucket_graph(self, kind: str, bucket: int):
-        key = (kind, bucket)
+    def _replay(self, key: tuple, fn, prepare=None):
+        """``fn()`` of a small-job step on ``bucket`` rows staged in slot 0. A graph engine captures it once
+        per ``key`` and replays it, returning the capture's static outputs; on a miss ``prepare()`` (inputs
+        built lazily, which must not be built inside a capture) and a warm-up run come first."""
+        if not self.use_graph:
+            return fn()
         if key not in self._bgraphs:
-            ids, lens = self.ids_s[0][:bucket], self.lens_s[0][:bucket]
-
-            def fn():
-                if kind == "text":
-                    self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
-                return self.model.forward(ids, lens, self.k)
-
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):  # warm-up off-graph
-                fn()
-            torch.cuda.current_stream(self.device).wait_stream(s)
+            if self._bpool is None:
+                self._bpool = torch.cuda.graph_pool_handle()
+            if prepare is not None:
+                prepare()
+            self._warm(fn)
             self._bgraphs[key] = capture_graph(fn, pool=self._bpool)
-        return self._bgraphs[key]
+        g, outs = self._bgraphs[key]
+        g.replay()
+        return outs
+
+    def _stage_texts(self, chunk: Tuple[np.ndarray, np.ndarray], n: int) -> int:
+        """The packed ``(text, offs)`` of ``n`` rows, through the pinned rows into slot 0, padded with empty
+        strings up to the bucket of ``n``, which is returned. The copies are asynchronous: the caller does
+        not overwrite the pinned rows (the next call) before something it waits for is ordered after them."""
+        text, offs = chunk
+        pin = self._pinned()
+        bk = self._bucket(n)
+        pin["text"][:text.size].copy_(torch.from_numpy(text))
+        pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
+        pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
+        if text.size:
+            self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
+        self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
+        return bk
+
+    def _result_rows(self, name: str, rows: int, floor: int, *specs) -> Tuple[torch.Tensor, ...]:
+        """The first ``rows`` rows of the engine's result buffers ``self.<name>``, one ``[cap, *shape]`` tensor
+        per ``(shape, dtype)`` of ``specs``: allocated at ``max(rows, floor)`` rows on first use, again when
+        ``rows`` outgrows them or the row shape changes. Views, valid until the next call."""
+        bufs = getattr(self, name, None)
+        if bufs is None or bufs[0].shape[0] < rows or tuple(bufs[0].shape[1:]) != specs[0][0]:
+            cap = max(rows, floor)
+            bufs = tuple(torch.empty((cap,) + shape, dtype=dtype, device=self.device) for shape, dtype in specs)
+            setattr(self, name, bufs)
+        return tuple(t[:rows] for t in bufs)
 
     def _run_bucket(self, kind: str, m: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         bk = self._bucket(m)
-        if self.use_graph:
-            g, (_, idx, sc) = self._bucket_graph(kind, bk)
-            g.replay()
-        else:
+
+        def fn():
             if kind == "text":
                 self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bk)
-            _, idx, sc = self.model.forward(self.ids_s[0][:bk], self.lens_s[0][:bk], self.k)
+            return self.model.forward(self.ids_s[0][:bk], self.lens_s[0][:bk], self.k)
+
+        _, idx, sc = self._replay((kind, bk), fn)
         both = torch.cat([idx[:m, :k].view(torch.float32), sc[:m, :k]], 1).cpu()  # one D2H, one sync
         return both[:, :k].contiguous().view(torch.int32), both[:, k:].contiguous()
 
@@ -360,15 +391,8 @@ class ClassifyEngine:
                                    r.encode("utf-8")[:self.max_row_bytes] for r in chunk)
             n = len(chunk)
             if self.device.type == "cuda":
-                pin = self._pinned()
-                bk = self._bucket(n)
-                pin["text"][:text.size].copy_(torch.from_numpy(text))
-                pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
-                pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
-                if text.size:
-                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
-                self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
-                i, s_ = self._run_bucket("text", n, min(k, self.k))
+                self._stage_texts((text, offs), n)
+                i, s_ = self._run_bucket("text", n, min(k, self.k))  # its D2H synchronizes: pinned rows free again
                 idx_all.append(i)
                 sc_all.append(s_)
             else:
@@ -490,13 +514,6 @@ class ClassifyEngine:
         self._tokenize(self.text[slot], self.offs[slot], ids=ids, lens=lens, rows=rows)
         return self.model.embed(ids[:rows], lens[:rows], key[0], key[1])
 
-    def _warm(self, fn) -> None:
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):  # warm up allocator + code objects off-graph
-            fn()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-
     def _embed_graph_step(self, slot: int, key: Tuple[str, bool]) -> torch.Tensor:
         gk = (slot,) + key
         if gk not in self._egraphs:
@@ -526,15 +543,7 @@ class ClassifyEngine:
             self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
             return self.model.embed(self.ids_s[0][:bucket], self.lens_s[0][:bucket], key[0], key[1])
 
-        if not self.use_graph:
-            return fn()
-        gk = ("embed", bucket) + key
-        if gk not in self._bgraphs:
-            self._warm(fn)
-            self._bgraphs[gk] = capture_graph(fn, pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
+        return self._replay(("embed", bucket) + key, fn)
 
     def embed_texts(self, rows: Sequence, pooling: str = "mean", normalize: bool = True) -> EmbedResult:
         """Embed an in-memory list of strings (small jobs; no CSV) -> host fp32 ``[n, H]``."""
@@ -546,14 +555,7 @@ class ClassifyEngine:
                                    r.encode("utf-8")[:self.max_row_bytes] for r in chunk)
             n = len(chunk)
             if self.device.type == "cuda":
-                pin = self._pinned()
-                bk = self._bucket(n)
-                pin["text"][:text.size].copy_(torch.from_numpy(text))
-                pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
-                pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
-                if text.size:
-                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
-                self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
+                bk = self._stage_texts((text, offs), n)
                 out.append(self._embed_bucket(bk, key)[:n].cpu())  # the D2H synchronizes: pinned rows free again
             else:
                 ids, lens = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
@@ -652,10 +654,6 @@ class ClassifyEngine:
         for the queries, the pair rows with their type ids, and the rows' query index."""
         if getattr(self, "_rr", None) is None:
             dev, B, S = self.device, self.B, self.S
-
-            def i32(*shape, **kw):
-                return torch.zeros(shape, dtype=torch.int32, **kw)
-
             rr = {"text_q": torch.empty(B * self.max_row_bytes, dtype=torch.uint8, device=dev),
                   "offs_q": i32(B + 1, device=dev), "ids_q": i32(B, S, device=dev), "lens_q": i32(B, device=dev),
                   "ids": i32(B, S, device=dev), "type_ids": i32(B, S, device=dev), "lens": i32(B, device=dev),
@@ -666,27 +664,20 @@ class ClassifyEngine:
             self._rr = rr
         return self._rr
 
-    def _rerank_step(self, bucket: int, mq: int, label: int) -> torch.Tensor:
-        """Raw scores ``[bucket]`` of the pairs staged in slot 0 (passages) and the query slot."""
+    def _assemble_pairs(self, bucket: int, mq: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The pair rows ``(ids, lens, type_ids)`` of the pairs staged in slot 0 (passages) and the query slot."""
         r = self._rerank_bufs()
         cls_id, sep_id, pad_id = self._special_ids()
         self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
         self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
         ops.pair_assemble(r["ids_q"][:bucket], r["lens_q"][:bucket], self.ids_s[0], self.lens_s[0], r["qidx"], mq,
                           cls_id, sep_id, pad_id, ids=r["ids"], type_ids=r["type_ids"], lens=r["lens"], rows=bucket)
-        return self.model.score(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], label)
+        return r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket]
 
-    def _rerank_bucket(self, bucket: int, mq: int, label: int) -> torch.Tensor:
-        if not self.use_graph:
-            return self._rerank_step(bucket, mq, label)
-        gk = ("rerank", bucket, mq, label)
-        if gk not in self._bgraphs:
-            # the WordPiece table is on the device since __init__; the warm-up run loads the code objects
-            self._warm(lambda: self._rerank_step(bucket, mq, label))
-            self._bgraphs[gk] = capture_graph(lambda: self._rerank_step(bucket, mq, label), pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
+    def _rerank_step(self, bucket: int, mq: int, label: int) -> torch.Tensor:
+        """Raw scores ``[bucket]`` of the staged pairs."""
+        ids, lens, types = self._assemble_pairs(bucket, mq)
+        return self.model.score(ids, lens, types, label)
 
     def _encode_rows(self, rows: Sequence) -> List[bytes]:
         return [(r if isinstance(r, (bytes, bytearray)) else r.encode("utf-8"))[:self.max_row_bytes] for r in rows]
@@ -720,7 +711,9 @@ class ClassifyEngine:
                 ids, types, lens = rows
                 scores[c0:c0 + m] = self.model.score(ids, lens, types, label)
             else:
-                scores[c0:c0 + m].copy_(self._rerank_bucket(bk, mq, label)[:m])
+                # the WordPiece table is on the device since __init__; the warm-up run loads the code objects
+                out = self._replay(("rerank", bk, mq, label), lambda: self._rerank_step(bk, mq, label))
+                scores[c0:c0 + m].copy_(out[:m])
         return scores
 
     def _pair_chunks(self, queries: Sequence, passages: Sequence, goff: List[int], mq: int, wide: bool = False):
@@ -738,7 +731,6 @@ class ClassifyEngine:
             return
         qid = np.repeat(np.arange(Q, dtype=np.int64), np.diff(np.asarray(goff, dtype=np.int64)))  # row -> query
         r = self._rerank_bufs()
-        pin = self._pinned() if cuda else None
         free = None  # the event after which the pinned rows of the previous chunk may be overwritten
         for c0 in range(0, P, self.B):
             m = min(self.B, P - c0)
@@ -757,20 +749,14 @@ class ClassifyEngine:
                 yield c0, m, None, ops.pair_assemble(ids_q, lens_q, ids_p, lens_p, torch.from_numpy(local), mq,
                                                      *self._special_ids())
                 continue
-            bk, nq = self._bucket(m), len(used)
             if free is not None:
                 free.synchronize()
-            pin["text"][:text_p.size].copy_(torch.from_numpy(text_p))
-            pin["offs"][:m + 1].copy_(torch.from_numpy(offs_p))
-            pin["offs"][m + 1:bk + 1].fill_(int(offs_p[-1]))  # padding rows: an empty passage ...
+            bk, nq = self._stage_texts((text_p, offs_p), m), len(used)  # padding rows: an empty passage ...
             r["pin_text_q"][:text_q.size].copy_(torch.from_numpy(text_q))
             r["pin_offs_q"][:nq + 1].copy_(torch.from_numpy(offs_q))
             r["pin_offs_q"][nq + 1:bk + 1].fill_(int(offs_q[-1]))
             r["pin_qidx"][:m].copy_(torch.from_numpy(local))
             r["pin_qidx"][m:bk].zero_()  # ... of query 0, their scores dropped
-            if text_p.size:
-                self.text[0][:text_p.size].copy_(pin["text"][:text_p.size], non_blocking=True)
-            self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
             if text_q.size:
                 r["text_q"][:text_q.size].copy_(r["pin_text_q"][:text_q.size], non_blocking=True)
             r["offs_q"][:bk + 1].copy_(r["pin_offs_q"][:bk + 1], non_blocking=True)
@@ -787,25 +773,8 @@ class ClassifyEngine:
     # spans into [P, n] buffers; after the last chunk one group_topk launch over the flattened
     # [P * n] scores and one D2H. The host maps the returned token spans to character offsets.
     def _answer_step(self, bucket: int, mq: int, max_len: int, n: int):
-        r = self._rerank_bufs()
-        cls_id, sep_id, pad_id = self._special_ids()
-        self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
-        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
-        ops.pair_assemble(r["ids_q"][:bucket], r["lens_q"][:bucket], self.ids_s[0], self.lens_s[0], r["qidx"], mq,
-                          cls_id, sep_id, pad_id, ids=r["ids"], type_ids=r["type_ids"], lens=r["lens"], rows=bucket)
-        return self.model.spans(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], max_len, n)
-
-    def _answer_bucket(self, bucket: int, mq: int, max_len: int, n: int):
-        if not self.use_graph:
-            return self._answer_step(bucket, mq, max_len, n)
-        gk = ("answer", bucket, mq, max_len, n)
-        if gk not in self._bgraphs:
-            self.model.span_inputs()  # built here, not inside the capture
-            self._warm(lambda: self._answer_step(bucket, mq, max_len, n))
-            self._bgraphs[gk] = capture_graph(lambda: self._answer_step(bucket, mq, max_len, n), pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
+        ids, lens, types = self._assemble_pairs(bucket, mq)
+        return self.model.spans(ids, lens, types, max_len, n)
 
     def _check_answer_args(self, top_k, max_answer_tokens, max_query_tokens) -> Tuple[int, int, int]:
         if self.S < 4:
@@ -839,13 +808,9 @@ class ClassifyEngine:
         if doc_stride is not None and (isinstance(doc_stride, bool) or not isinstance(doc_stride, int)
                                        or not 1 <= doc_stride <= self.S - 3):
             raise ValueError("doc_stride must be an int in [1, seq_len - 3]")
-        dev = self.device
-        if getattr(self, "_an", None) is None or self._an[0].shape[0] < P or self._an[0].shape[1] != n:
-            rows = max(P, self.B)  # one allocation serves every job of up to B pairs
-            self._an = (torch.empty((rows, n, 2), dtype=torch.int32, device=dev),
-                        torch.empty((rows, n), dtype=torch.float32, device=dev),
-                        torch.empty((rows,), dtype=torch.float32, device=dev))
-        span, score, null = (t[:P] for t in self._an)
+        # one allocation serves every job of up to B pairs
+        span, score, null = self._result_rows("_an", P, self.B, ((n, 2), torch.int32), ((n,), torch.float32),
+                                              ((), torch.float32))
         if doc_stride is not None:
             self._span_windows(questions, passages, goff, n, ma, mq, doc_stride, span, score, null)
             return span, score, null
@@ -854,7 +819,8 @@ class ClassifyEngine:
                 ids, types, lens = rows
                 sp, sc, nl = self.model.spans(ids, lens, types, ma, n)
             else:
-                sp, sc, nl = self._answer_bucket(bk, mq, ma, n)
+                sp, sc, nl = self._replay(("answer", bk, mq, ma, n), lambda: self._answer_step(bk, mq, ma, n),
+                                          prepare=self.model.span_inputs)
             span[c0:c0 + m].copy_(sp[:m]), score[c0:c0 + m].copy_(sc[:m]), null[c0:c0 + m].copy_(nl[:m])
         return span, score, null
 
@@ -871,10 +837,6 @@ class ClassifyEngine:
         if getattr(self, "_wn", None) is None:
             dev, B = self.device, self.B
             L = self.max_row_bytes + 2
-
-            def i32(*shape, **kw):
-                return torch.zeros(shape, dtype=torch.int32, **kw)
-
             w = {"ids_p": i32(B, L, device=dev), "lens_p": i32(B, device=dev), "win_pair": i32(B, device=dev),
                  "win_start": i32(B, device=dev), "own": i32(B, 2, device=dev), "wrow": i32(B + 1, device=dev)}
             if dev.type == "cuda":
@@ -889,15 +851,6 @@ class ClassifyEngine:
         self._tokenize(self.text[0], self.offs[0], ids=w["ids_p"], lens=w["lens_p"], rows=bucket,
                        seq_len=self.max_row_bytes + 2)
 
-    def _wtok_bucket(self, bucket: int) -> None:
-        if not self.use_graph:
-            return self._wtok_step(bucket)
-        gk = ("wtok", bucket)
-        if gk not in self._bgraphs:
-            self._warm(lambda: self._wtok_step(bucket))
-            self._bgraphs[gk] = capture_graph(lambda: self._wtok_step(bucket), pool=self._bpool)
-        self._bgraphs[gk][0].replay()
-
     def _wanswer_step(self, bucket: int, mq: int, max_len: int, n: int, doc_stride: int):
         r, w = self._rerank_bufs(), self._window_bufs()
         cls_id, sep_id, pad_id = self._special_ids()
@@ -906,30 +859,6 @@ class ClassifyEngine:
                             type_ids=r["type_ids"], lens=r["lens"], own=w["own"], rows=bucket)
         return self.model.spans(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], max_len, n,
                                 own=w["own"])
-
-    def _wanswer_bucket(self, bucket: int, mq: int, max_len: int, n: int, doc_stride: int):
-        if not self.use_graph:
-            return self._wanswer_step(bucket, mq, max_len, n, doc_stride)
-        gk = ("wanswer", bucket, mq, max_len, n, doc_stride)
-        if gk not in self._bgraphs:
-            self.model.span_inputs()  # built here, not inside the capture
-            self._warm(lambda: self._wanswer_step(bucket, mq, max_len, n, doc_stride))
-            self._bgraphs[gk] = capture_graph(lambda: self._wanswer_step(bucket, mq, max_len, n, doc_stride),
-                                              pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
-
-    def _window_rows_bufs(self, R: int, n: int) -> Tuple[torch.Tensor, ...]:
-        """``(span_w [R, n, 2], score_w [R, n], null_w [R], start_w [R])`` for a pair chunk's window rows:
-        grown here, outside any capture."""
-        if getattr(self, "_wr", None) is None or self._wr[0].shape[0] < R or self._wr[0].shape[1] != n:
-            rows, dev = max(R, 2 * self.B), self.device
-            self._wr = (torch.empty((rows, n, 2), dtype=torch.int32, device=dev),
-                        torch.empty((rows, n), dtype=torch.float32, device=dev),
-                        torch.empty((rows,), dtype=torch.float32, device=dev),
-                        torch.empty((rows,), dtype=torch.int32, device=dev))
-        return tuple(t[:R] for t in self._wr)
 
     def _span_windows(self, questions: Sequence, passages: Sequence, goff: List[int], n: int, ma: int, mq: int,
                       doc_stride: int, span: torch.Tensor, score: torch.Tensor, null: torch.Tensor) -> None:
@@ -944,7 +873,7 @@ class ClassifyEngine:
                 ids_q, lens_q, ids_p, lens_p, qidx = rows
                 lq, lp, qi = lens_q.tolist(), lens_p.tolist(), qidx.tolist()
             else:
-                self._wtok_bucket(bk)
+                self._replay(("wtok", bk), lambda: self._wtok_step(bk))
                 host = torch.cat([r["lens_q"][:bk], w["lens_p"][:bk], r["qidx"][:bk]]).cpu()  # one D2H, one sync
                 lq, lp, qi = (host[i * bk:(i + 1) * bk].tolist() for i in range(3))
             pair_l, start_l, wrow = [], [], [0]
@@ -965,7 +894,9 @@ class ClassifyEngine:
                 sp, sc, nl = self.model.spans(ids, lens, types, ma, n, own=own)
                 ops.window_best(sp, sc, nl, win_start, wrow_t, span=span[c0:], score=score[c0:], null=null[c0:])
                 continue
-            span_w, score_w, null_w, start_w = self._window_rows_bufs(R, n)
+            # the chunk's window rows: grown here, outside any capture
+            span_w, score_w, null_w, start_w = self._result_rows(
+                "_wr", R, 2 * B, ((n, 2), torch.int32), ((n,), torch.float32), ((), torch.float32), ((), torch.int32))
             for r0 in range(0, R, B):
                 mw = min(B, R - r0)
                 bkw = self._bucket(mw)
@@ -982,7 +913,9 @@ class ClassifyEngine:
                 w["win_start"][:bkw].copy_(w["pin_start"][:bkw], non_blocking=True)
                 wfree = torch.cuda.Event()
                 wfree.record()
-                sp, sc, nl = self._wanswer_bucket(bkw, mq, ma, n, doc_stride)
+                sp, sc, nl = self._replay(("wanswer", bkw, mq, ma, n, doc_stride),
+                                          lambda: self._wanswer_step(bkw, mq, ma, n, doc_stride),
+                                          prepare=self.model.span_inputs)
                 span_w[r0:r0 + mw].copy_(sp[:mw]), score_w[r0:r0 + mw].copy_(sc[:mw])
                 null_w[r0:r0 + mw].copy_(nl[:mw]), start_w[r0:r0 + mw].copy_(w["win_start"][:mw])
             ops.window_best(span_w, score_w, null_w, start_w, w["wrow"][:m + 1], span=span[c0:], score=score[c0:],
@@ -1125,18 +1058,6 @@ class ClassifyEngine:
         return self.model.tags(self.ids_s[0][:bucket], self.lens_s[0][:bucket], st["label_type"], st["label_begin"],
                                mode, E, cont=self._tag_cont() if mode == 2 else None)
 
-    def _tag_bucket(self, bucket: int, mode: int, E: int):
-        if not self.use_graph:
-            return self._tag_step(bucket, mode, E)
-        gk = ("tag", bucket, mode, E)
-        if gk not in self._bgraphs:
-            self.model.tag_inputs()  # built here, not inside the capture
-            self._warm(lambda: self._tag_step(bucket, mode, E))
-            self._bgraphs[gk] = capture_graph(lambda: self._tag_step(bucket, mode, E), pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
-
     def tag_rows(self, rows: Sequence, mode="simple", max_entities: int = 64
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The entity records of every row: ``(ent [N, E, 4] int32, ent_sum [N, E] fp32, count [N] int32)`` of
@@ -1149,26 +1070,17 @@ class ClassifyEngine:
         if mode == 2:
             self._tag_cont()
         N, dev = len(rows), self.device
-        if getattr(self, "_tg", None) is None or self._tg[0].shape[0] < N or self._tg[0].shape[1] != E:
-            cap = max(N, self.B)  # one allocation serves every job of up to B rows
-            self._tg = (torch.empty((cap, E, 4), dtype=torch.int32, device=dev),
-                        torch.empty((cap, E), dtype=torch.float32, device=dev),
-                        torch.empty((cap,), dtype=torch.int32, device=dev))
-        ent, ent_sum, count = (t[:N] for t in self._tg)
+        # one allocation serves every job of up to B rows
+        ent, ent_sum, count = self._result_rows("_tg", N, self.B, ((E, 4), torch.int32), ((E,), torch.float32),
+                                                ((), torch.int32))
         for b0 in range(0, N, self.B):
             chunk = self._encode_rows(rows[b0:b0 + self.B])
             text, offs = pack_rows(chunk)
             n = len(chunk)
             if dev.type == "cuda":
-                pin = self._pinned()
-                bk = self._bucket(n)
-                pin["text"][:text.size].copy_(torch.from_numpy(text))
-                pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
-                pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
-                if text.size:
-                    self.text[0][:text.size].copy_(pin["text"][:text.size], non_blocking=True)
-                self.offs[0][:bk + 1].copy_(pin["offs"][:bk + 1], non_blocking=True)
-                e, s_, c = self._tag_bucket(bk, mode, E)
+                bk = self._stage_texts((text, offs), n)
+                e, s_, c = self._replay(("tag", bk, mode, E), lambda: self._tag_step(bk, mode, E),
+                                        prepare=self.model.tag_inputs)
                 ent[b0:b0 + n].copy_(e[:n]), ent_sum[b0:b0 + n].copy_(s_[:n]), count[b0:b0 + n].copy_(c[:n])
                 torch.cuda.current_stream(dev).synchronize()  # the pinned rows are free again
             else:
@@ -1254,10 +1166,6 @@ class ClassifyEngine:
         if getattr(self, "_fl", None) is None:
             dev, B, S = self.device, self.B, self.S
             segcap, rcap = (MAX_MASKS + 1) * B, MAX_MASKS * B
-
-            def i32(*shape, **kw):
-                return torch.zeros(shape, dtype=torch.int32, **kw)
-
             fl = {"offs": i32(segcap + 1, device=dev), "ids_s": i32(segcap, S, device=dev),
                   "lens_s": i32(segcap, device=dev), "segoff": i32(B + 1, device=dev), "ids": i32(B, S, device=dev),
                   "lens": i32(B, device=dev), "pos": i32(B, MAX_MASKS, device=dev), "mrow": i32(rcap, device=dev),
@@ -1277,18 +1185,6 @@ class ClassifyEngine:
         tok, _, prob, _ = self.model.fills(f["ids"][:bucket], f["lens"][:bucket], f["pos"][:bucket], f["mrow"][:slots],
                                            f["mord"][:slots], k, tids=f["tids"][:T] if T else None)
         return tok, prob, f["pos"]
-
-    def _fill_bucket(self, bucket: int, segs: int, slots: int, k: int, T: int):
-        if not self.use_graph:
-            return self._fill_step(bucket, segs, slots, k, T)
-        gk = ("fill", bucket, segs, slots, k, T)
-        if gk not in self._bgraphs:
-            self.model.fill_inputs()  # built here, not inside the capture
-            self._warm(lambda: self._fill_step(bucket, segs, slots, k, T))
-            self._bgraphs[gk] = capture_graph(lambda: self._fill_step(bucket, segs, slots, k, T), pool=self._bpool)
-        g, out = self._bgraphs[gk]
-        g.replay()
-        return out
 
     def _slot_bucket(self, R: int) -> int:
         b = 16
@@ -1374,7 +1270,8 @@ class ClassifyEngine:
                 f["segoff"][:bk + 1].copy_(f["pin_segoff"][:bk + 1], non_blocking=True)
                 f["mrow"][:Rb].copy_(f["pin_mrow"][:Rb], non_blocking=True)
                 f["mord"][:Rb].copy_(f["pin_mord"][:Rb], non_blocking=True)
-                t_, p_, ps_ = self._fill_bucket(bk, segs, Rb, k, T)
+                t_, p_, ps_ = self._replay(("fill", bk, segs, Rb, k, T), lambda: self._fill_step(bk, segs, Rb, k, T),
+                                           prepare=self.model.fill_inputs)
                 if R:
                     dst = (f["mrow"][:R].long() + b0) * M + f["mord"][:R].long()
                     tok.view(N * M, kk).index_copy_(0, dst, t_[:R])
@@ -1479,7 +1376,7 @@ class ClassifyEngine:
         if self.vocab is not None and self.device.type == "cuda":
             extra += self.vocab.table_bytes  # the WordPiece table on this device
         # embed: the static [rows, H] fp32 outputs its graphs hold (nothing until the first embed call)
-        egraphs = list(self._egraphs.values()) + [v for k, v in (getattr(self, "_bgraphs", None) or {}).items()
+        egraphs = list(self._egraphs.values()) + [v for k, v in self._bgraphs.items()
                                                   if k[0] == "embed"]
         extra += sum(o.numel() * o.element_size() for _, o in egraphs)
         # rerank: its query slot, pair rows and type ids (nothing until the first rerank call)
@@ -1487,7 +1384,7 @@ class ClassifyEngine:
         # answer: the [P, n] span buffers, the span head's fp32 forms and its graphs' static outputs
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_an", None) or ()))
         extra += sum(t.numel() * t.element_size() for t in (getattr(self.model, "_span_inputs", None) or {}).values())
-        extra += sum(o.numel() * o.element_size() for k, (_, outs) in (getattr(self, "_bgraphs", None) or {}).items()
+        extra += sum(o.numel() * o.element_size() for k, (_, outs) in self._bgraphs.items()
                      if k[0] in ("answer", "wanswer") for o in outs)
         # windowed answer: the long passage rows, the window table and the [R, n] window-row buffers
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_wn", None) or {}).values() if t.is_cuda)

@@ -18,10 +18,10 @@ all-gathered and rank 0 ranks them. Errors are ``ValueError`` s with the fixed m
 from __future__ import annotations
 
 import math
-import time
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
+from ._common import is_int
 
 OP_NAME = "map_answer"
 MAX_TOP_K = 32
@@ -58,57 +58,32 @@ class Options(NamedTuple):
     doc_stride: Optional[int] = None  # None: one row per pair, the passage cut at the row's end
 
 
-def _is_int(v: Any) -> bool:
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work. The bounds
     that depend on the model (``max_answer_tokens``, ``max_query_tokens``) are checked by
     :func:`check_model` once it is loaded."""
     top_k = payload.get("top_k", 3)
-    if not _is_int(top_k) or not 1 <= top_k <= MAX_TOP_K:
+    if not is_int(top_k) or not 1 <= top_k <= MAX_TOP_K:
         raise ValueError(ERRORS["top_k"])
     ma = payload.get("max_answer_tokens", 30)
-    if not _is_int(ma) or ma < 1:
+    if not is_int(ma) or ma < 1:
         raise ValueError(ERRORS["max_answer_tokens"])
     mq = payload.get("max_query_tokens")
-    if mq is not None and (not _is_int(mq) or mq < 1):
+    if mq is not None and (not is_int(mq) or mq < 1):
         raise ValueError(ERRORS["max_query_tokens"])
-    margin = payload.get("min_score_over_null")
-    if margin is not None:
-        if isinstance(margin, bool) or not isinstance(margin, (int, float)) or margin != margin:
-            raise ValueError(ERRORS["min_score_over_null"])
-        margin = float(margin)
+    margin = _jobs.number_or_none(payload, "min_score_over_null", ERRORS["min_score_over_null"])
     nulls = payload.get("return_null_scores", False)
     if not isinstance(nulls, bool):
         raise ValueError(ERRORS["return_null_scores"])
     stride = payload.get("doc_stride")
-    if stride is not None and (not _is_int(stride) or stride < 1):
+    if stride is not None and (not is_int(stride) or stride < 1):
         raise ValueError(WINDOW_ERRORS["doc_stride"])
     return Options(top_k, ma, mq, margin, nulls, stride)
 
 
 def check_pairs(payload: Dict[str, Any]) -> Tuple[List[str], List[List[str]]]:
     """``(questions, passages per question)`` of either payload form."""
-    if "passages" not in payload or ("question" not in payload and "questions" not in payload):
-        raise ValueError(ERRORS["missing"])
-    if "question" in payload and "questions" in payload:
-        raise ValueError(ERRORS["both"])
-    passages = payload["passages"]
-    if "question" in payload:
-        if not isinstance(payload["question"], str):
-            raise ValueError(ERRORS["question"])
-        if not isinstance(passages, list) or not all(isinstance(p, str) for p in passages):
-            raise ValueError(ERRORS["passages"])
-        return [payload["question"]], [list(passages)]
-    questions = payload["questions"]
-    if not isinstance(questions, list) or not all(isinstance(q, str) for q in questions):
-        raise ValueError(ERRORS["questions"])
-    if (not isinstance(passages, list) or len(passages) != len(questions)
-            or not all(isinstance(ps, list) and all(isinstance(p, str) for p in ps) for ps in passages)):
-        raise ValueError(ERRORS["passage_lists"])
-    return list(questions), [list(ps) for ps in passages]
+    return _jobs.pairs_of(payload, "question", "questions", ERRORS)
 
 
 def check_model(h, opt: Options) -> None:
@@ -140,10 +115,10 @@ def result(h, opt: Options, questions: List[str], groups: List[List[str]], answe
                              "text": a["text"], "score": float(a["score"]), "null_score": float(a["null_score"]),
                              "probability": e / den} for a, e in zip(kept, ex)])
     n = sum(len(g) for g in groups)
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "query_count": len(questions),
            "pair_count": n, "top_k": opt.top_k, "max_answer_tokens": opt.max_answer_tokens,
-           "elapsed_ms": dt * 1000.0, "pairs_per_sec": (n / dt) if dt > 0 else None}
+           "elapsed_ms": elapsed_ms, "pairs_per_sec": rate}
     out.update(extra)
     out["answers"] = out_answers
     if opt.return_null_scores:
@@ -160,42 +135,31 @@ def answer_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
     over the DP ranks, the span / score / null rows all-gathered, ranked on rank 0 at the largest
     ``top_k``. A prefix of a total order is the smaller top-k, both among a pair's spans and among a
     question's, so each job gets exactly its single-job result; a bad payload gets its own error entry."""
-    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
-    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
 
-    out: List[Any] = [None] * len(payloads)
-    jobs = []
-    for i, p in enumerate(payloads):  # same payloads on every rank: same validation outcome
-        try:
-            opt = options(p)
-            questions, groups = check_pairs(p)
-            check_model(h, opt)
-            jobs.append((i, opt, questions, groups))
-        except Exception as exc:
-            out[i] = ("err", exc)
+    def check(p):
+        opt = options(p)
+        questions, groups = check_pairs(p)
+        check_model(h, opt)
+        return opt, questions, groups
+
+    out, jobs = _jobs.validated(payloads, check)
     if jobs:
         key = jobs[0][1]
         k = max(opt.top_k for _, opt, _, _ in jobs)
         questions = [q for _, _, qs, _ in jobs for q in qs]
         passages = [p for _, _, _, gs in jobs for g in gs for p in g]
-        goff = [0]
-        for _, _, _, gs in jobs:
-            for g in gs:
-                goff.append(goff[-1] + len(g))
-        exc, rows = None, None
-        try:
-            s_r, n_r = split_range(0, len(passages), ws, rank)
-            maybe_inject_fault("answer")
+        goff = _jobs.offsets([g for _, _, _, gs in jobs for g in gs])
+
+        def compute(s_r, n_r):
             # this rank's rows of every group; a question with none of them here costs nothing
             local = [min(max(g - s_r, 0), n_r) for g in goff]
             rows = h.engine.span_pairs(questions, passages[s_r:s_r + n_r], local, k, key.max_answer_tokens,
                                        key.max_query_tokens, key.doc_stride)
             if key.doc_stride is not None:  # every pair's window count travels with its rows
                 rows = tuple(rows) + (h.engine.window_counts,)
-        except Exception as e:
-            exc = e
-        counts = exchange_errors(exc, int(rows[0].shape[0]) if rows is not None else 0)
-        span, score, null, *wcount = all_gather_rows(*rows, counts=counts)
+            return rows
+
+        span, score, null, *wcount = _jobs.shard_and_gather("answer", len(passages), rank, ws, compute)
         if rank == 0:
             # windowed spans are tokens of the whole passage (cut at max_row_bytes), not of one row
             res = h.engine.rank_spans(span, score, null, passages, goff, k,
@@ -220,42 +184,17 @@ def answer_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
 def map_answer_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: jobs that share (model_path, max_query_tokens, max_answer_tokens, doc_stride) go to the device
     together; malformed payloads take the single-job path and fail alone."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for i, p in enumerate(payloads):
-        p = p or {}
-        try:
-            opt = options(p)
-            check_pairs(p)
-            groups.setdefault((p.get("model_path"), opt.max_query_tokens, opt.max_answer_tokens, opt.doc_stride),
-                              []).append(i)
-        except Exception:
-            try:
-                out[i] = ("ok", run(p))
-            except Exception as exc:
-                out[i] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[i], _op=OP_NAME, _t0=t0) for i in idxs]
-        try:
-            res = dispatch("map_answer_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for i, entry in zip(idxs, res):
-            out[i] = entry
-    return out
+    def key(p):
+        opt = options(p)
+        check_pairs(p)
+        return p.get("model_path"), opt.max_query_tokens, opt.max_answer_tokens, opt.doc_stride
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_answer_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:
-    payload = payload or {}
-    t0 = time.time()
-    from agent_tpu_amd.parallel.dp_ops import dispatch
-
-    options(payload)  # validated before any device work
-    check_pairs(payload)
-    return dispatch("map_answer", dict(payload, _op=OP_NAME, _t0=t0))
+    return _jobs.run_single(payload, OP_NAME, OP_NAME, lambda p: (options(p), check_pairs(p)))
 
 
 @register_op("map_answer")

@@ -20,7 +20,7 @@ import os
 import time
 from typing import Any, Dict, List, NamedTuple, Optional
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
 
 OP_NAME = "map_embed"
 
@@ -108,10 +108,9 @@ def result(h, emb, payload: Dict[str, Any], extra: Dict[str, Any]) -> Dict[str, 
     else:  # summary
         body["centroid"] = a32.mean(0, dtype=np.float64).tolist() if n else [0.0] * dim
         body["norm_mean"] = float(np.linalg.norm(a32.astype(np.float64), axis=1).mean()) if n else 0.0
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "row_count": n, "dim": dim,
-           "pooling": opt.pooling, "normalize": opt.normalize, "elapsed_ms": dt * 1000.0,
-           "rows_per_sec": (n / dt) if dt > 0 else None}
+           "pooling": opt.pooling, "normalize": opt.normalize, "elapsed_ms": elapsed_ms, "rows_per_sec": rate}
     out.update(extra)
     out.update(body)
     return out
@@ -160,32 +159,14 @@ def embed_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Option
 def map_embed_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``texts`` jobs that share (model_path, pooling, normalize) go to the device
     together; CSV-shard jobs (already large) and malformed payloads take the single-job path."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for i, p in enumerate(payloads):
-        p = p or {}
-        try:
-            if "texts" not in p:
-                raise KeyError("texts")
-            opt = options(p)
-            groups.setdefault((p.get("model_path"), opt.pooling, opt.normalize), []).append(i)
-        except Exception:
-            try:
-                out[i] = ("ok", run(p))
-            except Exception as exc:
-                out[i] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[i], _op=OP_NAME, _t0=t0) for i in idxs]
-        try:
-            res = dispatch("map_embed_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for i, entry in zip(idxs, res):
-            out[i] = entry
-    return out
+    def key(p):
+        if "texts" not in p:
+            raise KeyError("texts")  # not batchable
+        opt = options(p)
+        return p.get("model_path"), opt.pooling, opt.normalize
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_embed_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:

@@ -15,10 +15,10 @@ fallback stub.
 """
 from __future__ import annotations
 
-import time
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
+from ._common import is_int
 
 OP_NAME = "map_fill"
 MAX_TOP_K = 32
@@ -52,15 +52,14 @@ class Options(NamedTuple):
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work."""
     k = payload.get("top_k", 5)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_TOP_K:
+    if not is_int(k) or not 1 <= k <= MAX_TOP_K:
         raise ValueError(ERRORS["top_k"])
     mt = payload.get("mask_token", "[MASK]")
     if not isinstance(mt, str) or not mt:
         raise ValueError(ERRORS["mask_token"])
     tg = payload.get("targets")
     if tg is not None:
-        ok = isinstance(tg, list) and all((isinstance(t, str) and t) or (isinstance(t, int) and not isinstance(t, bool))
-                                          for t in tg)
+        ok = isinstance(tg, list) and all((isinstance(t, str) and t) or is_int(t) for t in tg)
         if not ok:
             raise ValueError(ERRORS["targets"])
         seen, uniq = set(), []
@@ -76,19 +75,7 @@ def options(payload: Dict[str, Any]) -> Options:
 
 def check_texts(payload: Dict[str, Any], opt: Options) -> List[str]:
     """The texts of either payload form; each must hold 1 to 16 mask tokens."""
-    if "text" not in payload and "texts" not in payload:
-        raise ValueError(ERRORS["missing"])
-    if "text" in payload and "texts" in payload:
-        raise ValueError(ERRORS["both"])
-    if "text" in payload:
-        if not isinstance(payload["text"], str):
-            raise ValueError(ERRORS["text"])
-        texts = [payload["text"]]
-    else:
-        texts = payload["texts"]
-        if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
-            raise ValueError(ERRORS["texts"])
-        texts = list(texts)
+    texts = _jobs.texts_of(payload, ERRORS)
     for i, t in enumerate(texts):
         n = t.count(opt.mask_token)
         if n == 0:
@@ -126,10 +113,10 @@ def result(h, opt: Options, texts: List[str], fills: List[List[Dict[str, Any]]],
            payload: Dict[str, Any], extra: Dict[str, Any]) -> Dict[str, Any]:
     """One job's result from the mapped ``fills`` of its texts and its ``truncated`` (text, mask) pairs (rank 0)."""
     n = len(texts)
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "row_count": n,
            "top_k": opt.top_k, "mask_token": opt.mask_token,
-           "elapsed_ms": dt * 1000.0, "rows_per_sec": (n / dt) if dt > 0 else None}
+           "elapsed_ms": elapsed_ms, "rows_per_sec": rate}
     out.update(extra)
     out["fills"] = fills
     out["truncated"] = [[int(i), int(j)] for i, j in truncated]
@@ -142,32 +129,19 @@ def fill_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optiona
     tok / prob / pos rows all-gathered and mapped on rank 0. A text's candidates do not depend on the texts it
     shares a batch with, so each job gets exactly its single-job result; a bad payload gets its own error
     entry."""
-    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
-    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
 
-    out: List[Any] = [None] * len(payloads)
-    jobs = []
-    for i, p in enumerate(payloads):  # same payloads on every rank: same validation outcome
-        try:
-            opt = options(p)
-            texts = check_texts(p, opt)
-            tids = check_model(h, opt)
-            jobs.append((i, opt, texts, tids))
-        except Exception as exc:
-            out[i] = ("err", exc)
+    def check(p):
+        opt = options(p)
+        return opt, check_texts(p, opt), check_model(h, opt)
+
+    out, jobs = _jobs.validated(payloads, check)
     if jobs:
         key, tids = jobs[0][1], jobs[0][3]
         texts = [t for _, _, ts, _ in jobs for t in ts]
         M = max([1] + [t.count(key.mask_token) for t in texts])  # every rank's rows have the same width
-        exc, rows = None, None
-        try:
-            s_r, n_r = split_range(0, len(texts), ws, rank)
-            maybe_inject_fault("fill")
-            rows = h.engine.fill_rows(texts[s_r:s_r + n_r], key.top_k, key.mask_token, tids, max_masks=M)
-        except Exception as e:
-            exc = e
-        counts = exchange_errors(exc, int(rows[0].shape[0]) if rows is not None else 0)
-        tok, prob, pos = all_gather_rows(*rows, counts=counts)
+        tok, prob, pos = _jobs.shard_and_gather(
+            "fill", len(texts), rank, ws,
+            lambda s_r, n_r: h.engine.fill_rows(texts[s_r:s_r + n_r], key.top_k, key.mask_token, tids, max_masks=M))
         if rank == 0:
             res = h.engine.map_fills(tok, prob, pos, texts, key.mask_token)
             r0 = 0
@@ -186,41 +160,18 @@ def fill_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optiona
 def map_fill_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: jobs that share (model_path, top_k, mask_token, targets) go to the device together;
     malformed payloads take the single-job path and fail alone."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for i, p in enumerate(payloads):
-        p = p or {}
-        try:
-            opt = options(p)
-            check_texts(p, opt)
-            tg = None if opt.targets is None else tuple((type(t).__name__, t) for t in opt.targets)
-            groups.setdefault((p.get("model_path"), opt.top_k, opt.mask_token, tg), []).append(i)
-        except Exception:
-            try:
-                out[i] = ("ok", run(p))
-            except Exception as exc:
-                out[i] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[i], _op=OP_NAME, _t0=t0) for i in idxs]
-        try:
-            res = dispatch("map_fill_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for i, entry in zip(idxs, res):
-            out[i] = entry
-    return out
+    def key(p):
+        opt = options(p)
+        check_texts(p, opt)
+        tg = None if opt.targets is None else tuple((type(t).__name__, t) for t in opt.targets)
+        return p.get("model_path"), opt.top_k, opt.mask_token, tg
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_fill_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:
-    payload = payload or {}
-    t0 = time.time()
-    from agent_tpu_amd.parallel.dp_ops import dispatch
-
-    check_texts(payload, options(payload))  # validated before any device work
-    return dispatch("map_fill", dict(payload, _op=OP_NAME, _t0=t0))
+    return _jobs.run_single(payload, OP_NAME, OP_NAME, lambda p: check_texts(p, options(p)))
 
 
 @register_op("map_fill")

@@ -15,10 +15,10 @@ all-gathered and rank 0 ranks them. Errors are ``ValueError`` s with the fixed m
 """
 from __future__ import annotations
 
-import time
 from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
+from ._common import is_int
 
 OP_NAME = "map_rerank"
 MAX_TOP_K = 32
@@ -50,22 +50,18 @@ class Options(NamedTuple):
     min_score: Optional[float]
 
 
-def _is_int(v: Any) -> bool:
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work. The
     bounds that depend on the model (``label``, ``max_query_tokens``) are checked by
     :func:`check_model` once it is loaded."""
     top_k = payload.get("top_k", 10)
-    if not _is_int(top_k) or not 1 <= top_k <= MAX_TOP_K:
+    if not is_int(top_k) or not 1 <= top_k <= MAX_TOP_K:
         raise ValueError(ERRORS["top_k"])
     mq = payload.get("max_query_tokens")
-    if mq is not None and (not _is_int(mq) or mq < 1):
+    if mq is not None and (not is_int(mq) or mq < 1):
         raise ValueError(ERRORS["max_query_tokens"])
     label = payload.get("label", 0)
-    if not _is_int(label) or label < 0:
+    if not is_int(label) or label < 0:
         raise ValueError(ERRORS["label"])
     activation = payload.get("activation", "none")
     if activation not in ("none", "sigmoid"):
@@ -73,34 +69,13 @@ def options(payload: Dict[str, Any]) -> Options:
     return_scores = payload.get("return_scores", False)
     if not isinstance(return_scores, bool):
         raise ValueError(ERRORS["return_scores"])
-    min_score = payload.get("min_score")
-    if min_score is not None:
-        if isinstance(min_score, bool) or not isinstance(min_score, (int, float)) or min_score != min_score:
-            raise ValueError(ERRORS["min_score"])
-        min_score = float(min_score)
+    min_score = _jobs.number_or_none(payload, "min_score", ERRORS["min_score"])
     return Options(top_k, mq, label, activation, return_scores, min_score)
 
 
 def check_pairs(payload: Dict[str, Any]) -> Tuple[List[str], List[List[str]]]:
     """``(queries, passages per query)`` of either payload form."""
-    if "passages" not in payload or ("query" not in payload and "queries" not in payload):
-        raise ValueError(ERRORS["missing"])
-    if "query" in payload and "queries" in payload:
-        raise ValueError(ERRORS["both"])
-    passages = payload["passages"]
-    if "query" in payload:
-        if not isinstance(payload["query"], str):
-            raise ValueError(ERRORS["query"])
-        if not isinstance(passages, list) or not all(isinstance(p, str) for p in passages):
-            raise ValueError(ERRORS["passages"])
-        return [payload["query"]], [list(passages)]
-    queries = payload["queries"]
-    if not isinstance(queries, list) or not all(isinstance(q, str) for q in queries):
-        raise ValueError(ERRORS["queries"])
-    if (not isinstance(passages, list) or len(passages) != len(queries)
-            or not all(isinstance(ps, list) and all(isinstance(p, str) for p in ps) for ps in passages)):
-        raise ValueError(ERRORS["passage_lists"])
-    return list(queries), [list(ps) for ps in passages]
+    return _jobs.pairs_of(payload, "query", "queries", ERRORS)
 
 
 def check_model(h, opt: Options) -> None:
@@ -127,10 +102,10 @@ def result(h, opt: Options, queries: List[str], groups: List[List[str]], idx, va
             row.append({"index": int(i), "score": float(s)})
         ranked.append(row)
     n = int(raw.numel())
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "query_count": len(queries),
            "pair_count": n, "top_k": opt.top_k, "label": opt.label, "activation": opt.activation,
-           "elapsed_ms": dt * 1000.0, "pairs_per_sec": (n / dt) if dt > 0 else None}
+           "elapsed_ms": elapsed_ms, "pairs_per_sec": rate}
     out.update(extra)
     out["ranked"] = ranked
     if opt.return_scores:
@@ -147,38 +122,26 @@ def rerank_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
     over the DP ranks, the scores all-gathered, ranked on rank 0 at the largest ``top_k``. A prefix
     of a total order is the smaller top-k, so each job gets exactly its single-job result; a bad
     payload gets its own error entry."""
-    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
-    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
 
-    out: List[Any] = [None] * len(payloads)
-    jobs = []
-    for i, p in enumerate(payloads):  # same payloads on every rank: same validation outcome
-        try:
-            opt = options(p)
-            queries, groups = check_pairs(p)
-            check_model(h, opt)
-            jobs.append((i, opt, queries, groups))
-        except Exception as exc:
-            out[i] = ("err", exc)
+    def check(p):
+        opt = options(p)
+        queries, groups = check_pairs(p)
+        check_model(h, opt)
+        return opt, queries, groups
+
+    out, jobs = _jobs.validated(payloads, check)
     if jobs:
         key = jobs[0][1]
         queries = [q for _, _, qs, _ in jobs for q in qs]
         passages = [p for _, _, _, gs in jobs for g in gs for p in g]
-        goff = [0]
-        for _, _, _, gs in jobs:
-            for g in gs:
-                goff.append(goff[-1] + len(g))
-        exc, scores = None, None
-        try:
-            s_r, n_r = split_range(0, len(passages), ws, rank)
-            maybe_inject_fault("rerank")
+        goff = _jobs.offsets([g for _, _, _, gs in jobs for g in gs])
+
+        def compute(s_r, n_r):
             # this rank's rows of every group; a query with none of them here costs nothing
             local = [min(max(g - s_r, 0), n_r) for g in goff]
-            scores = h.engine.score_pairs(queries, passages[s_r:s_r + n_r], local, key.max_query_tokens, key.label)
-        except Exception as e:
-            exc = e
-        counts = exchange_errors(exc, int(scores.shape[0]) if scores is not None else 0)
-        (scores,) = all_gather_rows(scores, counts=counts)
+            return (h.engine.score_pairs(queries, passages[s_r:s_r + n_r], local, key.max_query_tokens, key.label),)
+
+        (scores,) = _jobs.shard_and_gather("rerank", len(passages), rank, ws, compute)
         if rank == 0:
             k = max(opt.top_k for _, opt, _, _ in jobs)
             res = h.engine.rank_scores(scores, goff, k)
@@ -203,41 +166,17 @@ def rerank_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optio
 def map_rerank_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: jobs that share (model_path, max_query_tokens, label) go to the device together;
     malformed payloads take the single-job path and fail alone."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for i, p in enumerate(payloads):
-        p = p or {}
-        try:
-            opt = options(p)
-            check_pairs(p)
-            groups.setdefault((p.get("model_path"), opt.max_query_tokens, opt.label), []).append(i)
-        except Exception:
-            try:
-                out[i] = ("ok", run(p))
-            except Exception as exc:
-                out[i] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[i], _op=OP_NAME, _t0=t0) for i in idxs]
-        try:
-            res = dispatch("map_rerank_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for i, entry in zip(idxs, res):
-            out[i] = entry
-    return out
+    def key(p):
+        opt = options(p)
+        check_pairs(p)
+        return p.get("model_path"), opt.max_query_tokens, opt.label
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_rerank_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:
-    payload = payload or {}
-    t0 = time.time()
-    from agent_tpu_amd.parallel.dp_ops import dispatch
-
-    options(payload)  # validated before any device work
-    check_pairs(payload)
-    return dispatch("map_rerank", dict(payload, _op=OP_NAME, _t0=t0))
+    return _jobs.run_single(payload, OP_NAME, OP_NAME, lambda p: (options(p), check_pairs(p)))
 
 
 @register_op("map_rerank")

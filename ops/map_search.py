@@ -14,10 +14,9 @@ from __future__ import annotations
 
 import math
 import os
-import time
 from typing import Any, Dict, List, NamedTuple, Optional
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
 
 OP_NAME = "map_search"
 MAX_TOP_K = 32
@@ -197,10 +196,10 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         ids_l = [[row[j] for j in ks] for row, ks in zip(ids_l, keep)]
         sc_l = [[row[j] for j in ks] for row, ks in zip(sc_l, keep)]
     n = len(ids_l)
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out: Dict[str, Any] = {"ok": True, "op": payload.get("_op", OP_NAME), "query_count": n, "corpus_rows": total,
-                           "dim": dim, "top_k": top_k, "metric": opt.metric, "elapsed_ms": dt * 1000.0,
-                           "queries_per_sec": (n / dt) if dt > 0 else None}
+                           "dim": dim, "top_k": top_k, "metric": opt.metric, "elapsed_ms": elapsed_ms,
+                           "queries_per_sec": rate}
     if h is not None:
         out.update(model_path=h.model_path, pooling=opt.pooling)
     if ws > 1:
@@ -294,42 +293,18 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     corpus_uri, corpus_dtype) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs
     and malformed
     payloads take the single-job path."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for n, p in enumerate(payloads):
-        p = p or {}
-        try:
-            if "queries" not in p or "corpus_uri" not in p:
-                raise KeyError("queries")
-            opt = check_payload(p)
-            groups.setdefault((p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype),
-                              []).append(n)
-        except Exception:
-            try:
-                out[n] = ("ok", run(p))
-            except Exception as exc:
-                out[n] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[n], _op=OP_NAME, _t0=t0) for n in idxs]
-        try:
-            res = dispatch("map_search_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for n, entry in zip(idxs, res):
-            out[n] = entry
-    return out
+    def key(p):
+        if "queries" not in p or "corpus_uri" not in p:
+            raise KeyError("queries")  # not batchable
+        opt = check_payload(p)
+        return p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:
-    payload = payload or {}
-    t0 = time.time()
-    from agent_tpu_amd.parallel.dp_ops import dispatch
-
-    check_payload(payload)  # validated before any device work
-    return dispatch("map_search", dict(payload, _op=OP_NAME, _t0=t0))
+    return _jobs.run_single(payload, OP_NAME, OP_NAME, check_payload)
 
 
 @register_op("map_search")

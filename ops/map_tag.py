@@ -14,10 +14,10 @@ all-gathered and rank 0 maps them. Errors are ``ValueError`` s with the fixed me
 """
 from __future__ import annotations
 
-import time
 from typing import Any, Dict, List, NamedTuple, Optional
 
-from . import register_batch_op, register_op
+from . import _jobs, register_batch_op, register_op
+from ._common import is_int
 
 OP_NAME = "map_tag"
 MAX_ENTITIES = 512
@@ -49,30 +49,14 @@ def options(payload: Dict[str, Any]) -> Options:
     if not isinstance(agg, str) or agg not in AGGREGATIONS:
         raise ValueError(ERRORS["aggregation"])
     E = payload.get("max_entities", 64)
-    if isinstance(E, bool) or not isinstance(E, int) or not 1 <= E <= MAX_ENTITIES:
+    if not is_int(E) or not 1 <= E <= MAX_ENTITIES:
         raise ValueError(ERRORS["max_entities"])
-    ms = payload.get("min_score")
-    if ms is not None:
-        if isinstance(ms, bool) or not isinstance(ms, (int, float)) or ms != ms:
-            raise ValueError(ERRORS["min_score"])
-        ms = float(ms)
-    return Options(agg, E, ms)
+    return Options(agg, E, _jobs.number_or_none(payload, "min_score", ERRORS["min_score"]))
 
 
 def check_texts(payload: Dict[str, Any]) -> List[str]:
     """The texts of either payload form."""
-    if "text" not in payload and "texts" not in payload:
-        raise ValueError(ERRORS["missing"])
-    if "text" in payload and "texts" in payload:
-        raise ValueError(ERRORS["both"])
-    if "text" in payload:
-        if not isinstance(payload["text"], str):
-            raise ValueError(ERRORS["text"])
-        return [payload["text"]]
-    texts = payload["texts"]
-    if not isinstance(texts, list) or not all(isinstance(t, str) for t in texts):
-        raise ValueError(ERRORS["texts"])
-    return list(texts)
+    return _jobs.texts_of(payload, ERRORS)
 
 
 def check_model(h, opt: Options) -> None:
@@ -88,10 +72,10 @@ def result(h, opt: Options, texts: List[str], entities: List[List[Dict[str, Any]
     """One job's result from the mapped ``entities`` and true ``counts`` of its texts (rank 0)."""
     kept = [[e for e in row if opt.min_score is None or e["score"] >= opt.min_score] for row in entities]
     n = len(texts)
-    dt = time.time() - float(payload.get("_t0", time.time()))
+    elapsed_ms, rate = _jobs.timing(payload, n)
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "row_count": n,
            "aggregation": opt.aggregation, "max_entities": opt.max_entities,
-           "elapsed_ms": dt * 1000.0, "rows_per_sec": (n / dt) if dt > 0 else None}
+           "elapsed_ms": elapsed_ms, "rows_per_sec": rate}
     out.update(extra)
     out["entities"] = kept
     out["entity_counts"] = [int(c) for c in counts]
@@ -105,31 +89,20 @@ def tag_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
     ranks, the ent / ent_sum / count rows all-gathered and mapped on rank 0. A row's records do not
     depend on the rows it shares a batch with, so each job gets exactly its single-job result; a bad
     payload gets its own error entry."""
-    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
-    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
 
-    out: List[Any] = [None] * len(payloads)
-    jobs = []
-    for i, p in enumerate(payloads):  # same payloads on every rank: same validation outcome
-        try:
-            opt = options(p)
-            texts = check_texts(p)
-            check_model(h, opt)
-            jobs.append((i, opt, texts))
-        except Exception as exc:
-            out[i] = ("err", exc)
+    def check(p):
+        opt = options(p)
+        texts = check_texts(p)
+        check_model(h, opt)
+        return opt, texts
+
+    out, jobs = _jobs.validated(payloads, check)
     if jobs:
         key = jobs[0][1]
         texts = [t for _, _, ts in jobs for t in ts]
-        exc, rows = None, None
-        try:
-            s_r, n_r = split_range(0, len(texts), ws, rank)
-            maybe_inject_fault("tag")
-            rows = h.engine.tag_rows(texts[s_r:s_r + n_r], key.aggregation, key.max_entities)
-        except Exception as e:
-            exc = e
-        counts = exchange_errors(exc, int(rows[0].shape[0]) if rows is not None else 0)
-        ent, ent_sum, count = all_gather_rows(*rows, counts=counts)
+        ent, ent_sum, count = _jobs.shard_and_gather(
+            "tag", len(texts), rank, ws,
+            lambda s_r, n_r: h.engine.tag_rows(texts[s_r:s_r + n_r], key.aggregation, key.max_entities))
         if rank == 0:
             res = h.engine.map_tags(ent, ent_sum, count, texts, key.aggregation)
             r0 = 0
@@ -147,41 +120,17 @@ def tag_batch(h, payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 def map_tag_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: jobs that share (model_path, aggregation, max_entities) go to the device together;
     malformed payloads take the single-job path and fail alone."""
-    from agent_tpu_amd.parallel.dp_ops import dispatch
 
-    t0 = time.time()
-    out: List[Any] = [None] * len(payloads)
-    groups: Dict[Any, List[int]] = {}
-    for i, p in enumerate(payloads):
-        p = p or {}
-        try:
-            opt = options(p)
-            check_texts(p)
-            groups.setdefault((p.get("model_path"), opt.aggregation, opt.max_entities), []).append(i)
-        except Exception:
-            try:
-                out[i] = ("ok", run(p))
-            except Exception as exc:
-                out[i] = ("err", exc)
-    for idxs in groups.values():
-        descs = [dict(payloads[i], _op=OP_NAME, _t0=t0) for i in idxs]
-        try:
-            res = dispatch("map_tag_batch", {"payloads": descs})
-        except Exception as exc:
-            res = [("err", exc)] * len(idxs)
-        for i, entry in zip(idxs, res):
-            out[i] = entry
-    return out
+    def key(p):
+        opt = options(p)
+        check_texts(p)
+        return p.get("model_path"), opt.aggregation, opt.max_entities
+
+    return _jobs.lease_batch(payloads, OP_NAME, "map_tag_batch", key, run)
 
 
 def run(payload: Dict[str, Any], ctx: Dict[str, Any] = None) -> Dict[str, Any]:
-    payload = payload or {}
-    t0 = time.time()
-    from agent_tpu_amd.parallel.dp_ops import dispatch
-
-    options(payload)  # validated before any device work
-    check_texts(payload)
-    return dispatch("map_tag", dict(payload, _op=OP_NAME, _t0=t0))
+    return _jobs.run_single(payload, OP_NAME, OP_NAME, lambda p: (options(p), check_texts(p)))
 
 
 @register_op("map_tag")
