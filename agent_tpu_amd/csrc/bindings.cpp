@@ -418,6 +418,19 @@ PYBIND11_MODULE(_atpu, m) {
                          uintptr_t stream) {
     group_topk(P<const float>(scores), P<const int32_t>(goff), P<int32_t>(idx), P<float>(val), rows, Q, k, S(stream));
   });
+  m.def("premise_assemble",
+        [](uintptr_t ids_t, uintptr_t lens_t, uintptr_t ids_h, uintptr_t lens_h, uintptr_t tidx, uintptr_t hidx,
+           uintptr_t ids, uintptr_t type_ids, uintptr_t lens, int rows, int T, int Hn, int Sq, int mh, int cls, int sep,
+           int pad, uintptr_t stream) {
+          premise_assemble(P<const int32_t>(ids_t), P<const int32_t>(lens_t), P<const int32_t>(ids_h),
+                           P<const int32_t>(lens_h), P<const int32_t>(tidx), P<const int32_t>(hidx), P<int32_t>(ids),
+                           P<int32_t>(type_ids), P<int32_t>(lens), rows, T, Hn, Sq, mh, cls, sep, pad, S(stream));
+        });
+  m.def("nli_rank", [](uintptr_t pair, uintptr_t goff, uintptr_t order, uintptr_t score, int rows, int T, int mode,
+                       uintptr_t stream) {
+    nli_rank(P<const float>(pair), P<const int32_t>(goff), P<int32_t>(order), P<float>(score), rows, T, mode,
+             S(stream));
+  });
   m.def("span_topk",
         [](uintptr_t x, uintptr_t fin, uintptr_t u, uintptr_t su, uintptr_t c, uintptr_t type_ids, uintptr_t lens,
            uintptr_t span, uintptr_t score, uintptr_t null, uintptr_t logits, int B, int Sq, int H, int max_len, int n,

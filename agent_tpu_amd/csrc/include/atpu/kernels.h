@@ -325,6 +325,24 @@ void pair_assemble(const int32_t* ids_q, const int32_t* lens_q, const int32_t* i
 void group_topk(const float* scores, const int32_t* goff, int32_t* idx, float* val, int P, int Q, int k,
                 hipStream_t stream);
 
+// ------------------------------------------- zero-shot classification (zeroshot.hip)
+// Premise-first pair rows "atpu-premise v1" (agent_tpu_amd/tokenizer.py premise_rows is the twin): row r
+// with text row t = clamp(tidx[r], 0, T-1) and hypothesis row h = clamp(hidx[r], 0, Hn-1) becomes
+// [CLS] t_tok[0:nt] [SEP] h_tok[0:nh] [SEP] [PAD]..., nh = min(lens_h[h]-2, mh, S-3),
+// nt = min(lens_t[t]-2, S-3-nh) (lens clamped into [2, S]); type_ids 1 on the hypothesis and its
+// [SEP]; lens = nt + nh + 3. S >= 4, T >= 1, Hn >= 1, mh >= 0; nothing outside the P rows is touched.
+void premise_assemble(const int32_t* ids_t, const int32_t* lens_t, const int32_t* ids_h, const int32_t* lens_h,
+                      const int32_t* tidx, const int32_t* hidx, int32_t* ids, int32_t* type_ids, int32_t* lens, int P,
+                      int T, int Hn, int S, int mh, int cls, int sep, int pad, hipStream_t stream);
+// Label scores and the full ranking of every text's NLI logits pair [P, 2] = (entailment, contradiction):
+// group t is rows goff[t]..goff[t+1]-1 (goff [T+1], clamped into [0, P]). mode 1, and any group of one:
+// key e - c, score 1 / (1 + exp(-key)); mode 0: key e, score softmax over the group. A NaN logit (or
+// difference) makes the key -inf and the score 0; a group whose best key is -inf scores 0 throughout.
+// order [P] / score [P]: position goff[t] + r holds the group-local index and the score of the r-th
+// element in (key desc, index asc) order, +0.0 and -0.0 tie. Positions outside every group are not written.
+void nli_rank(const float* pair, const int32_t* goff, int32_t* order, float* score, int P, int T, int mode,
+              hipStream_t stream);
+
 // ------------------------------------------- question answering (span_head.hip)
 // Start / end logits of the pair rows x [B*S, H] and the n best answer spans of each row's passage.
 // With fin [B*S, 2] = (rstd, rstd*mu) the rows are raw and the LayerNorm is folded into the head:

@@ -720,3 +720,14 @@ class BertClassifier:
             raise ValueError("label must be in [0, num_labels)")
         logits, _, _ = self.forward(ids, lens, 1, type_ids=type_ids)
         return logits[:, int(label)]
+
+    def nli_logits(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor], ent: int,
+                   con: int) -> torch.Tensor:
+        """``[B, 2]`` fp32 ``(entailment, contradiction)`` logits of premise rows (``ops.premise_assemble``): the
+        raw logits of classes ``ent`` and ``con`` of :meth:`forward`. Integer slices and a stack: a list index
+        would build an index tensor, which a graph capture must not."""
+        C = self.cfg.num_labels
+        if not (0 <= int(ent) < C and 0 <= int(con) < C) or int(ent) == int(con):
+            raise ValueError("ent and con must be distinct labels in [0, num_labels)")
+        logits, _, _ = self.forward(ids, lens, 1, type_ids=type_ids)
+        return torch.stack([logits[:, int(ent)], logits[:, int(con)]], 1)

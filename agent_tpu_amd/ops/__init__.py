@@ -29,5 +29,6 @@ from .tag import (tag_entities, tag_ok, tag_logits_ref, tag_select_ref, tag_grou
                   default_tag_names)
 from .fill import (fill_assemble, fill_assemble_ref, mask_gather, mask_gather_ref, vocab_topk, vocab_topk_ok,  # noqa: F401
                    vocab_logits_ref, vocab_select_ref, vocab_topk_splits)
+from .zeroshot import premise_assemble, premise_assemble_ref, nli_rank, nli_rank_ref  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

@@ -17,9 +17,10 @@ Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
 ``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
 tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
 per-rank top-k lists, merged on rank 0) and, from the :data:`BATCHED_OPS`
-table, the ``map_rerank``, ``map_answer``, ``map_tag`` and ``map_fill`` tasks
-with their ``_batch`` forms (C2 all-gather of pair scores, span rows, entity
-records or mask candidates, ranked or mapped on rank 0).
+table, the ``map_rerank``, ``map_answer``, ``map_tag``, ``map_fill`` and
+``map_zero_shot`` tasks with their ``_batch`` forms (C2 all-gather of pair
+scores, span rows, entity records, mask candidates or NLI logits, ranked or
+mapped on rank 0).
 """
 from __future__ import annotations
 
@@ -565,13 +566,15 @@ def search_batch_task(payload: Dict[str, Any]) -> Any:
     return ms.search_batch(payload["payloads"], rank, ws)
 
 
-# ------------------------------------------- map_rerank, map_answer, map_tag, map_fill
+# ---------------------------- map_rerank, map_answer, map_tag, map_fill, map_zero_shot
 #: task name -> (``ops`` module, its batch function); every op has a single-job task under its own name
 #: and a ``_batch`` task for the jobs of one lease that share its group key
 BATCHED_OPS = {"map_rerank": ("map_rerank", "rerank_batch"), "map_rerank_batch": ("map_rerank", "rerank_batch"),
                "map_answer": ("map_answer", "answer_batch"), "map_answer_batch": ("map_answer", "answer_batch"),
                "map_tag": ("map_tag", "tag_batch"), "map_tag_batch": ("map_tag", "tag_batch"),
-               "map_fill": ("map_fill", "fill_batch"), "map_fill_batch": ("map_fill", "fill_batch")}
+               "map_fill": ("map_fill", "fill_batch"), "map_fill_batch": ("map_fill", "fill_batch"),
+               "map_zero_shot": ("map_zero_shot", "zero_shot_batch"),
+               "map_zero_shot_batch": ("map_zero_shot", "zero_shot_batch")}
 
 
 def _register_batched(name: str, module: str, batch_fn: str) -> None:

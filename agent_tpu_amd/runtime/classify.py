@@ -103,6 +103,28 @@ class FillResult:
 
 
 @dataclass
+class ZeroShotResult:
+    texts: int
+    pairs: int
+    goff: List[int]       # text t owns positions goff[t] .. goff[t + 1] - 1 of the rows below
+    order: torch.Tensor   # [pairs] int32 (host): position goff[t] + r = the index, within the text's labels, of its r-th
+    score: torch.Tensor   # [pairs] fp32 (host): ... and that label's score
+    logits: torch.Tensor  # [pairs, 2] fp32 (host): every pair's (entailment, contradiction) logits, in input order
+
+    def ranked(self, t: int) -> Tuple[List[int], List[float]]:
+        """``(label indices, scores)`` of text ``t``, best first."""
+        a, b = self.goff[t], self.goff[t + 1]
+        return self.order[a:b].tolist(), self.score[a:b].tolist()
+
+
+def _offsets(counts: Sequence[int]) -> List[int]:
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + int(c))
+    return off
+
+
+@dataclass
 class RunStats:
     rows: int = 0
     batches: int = 0
@@ -318,13 +340,14 @@ class ClassifyEngine:
         g.replay()
         return outs
 
-    def _stage_texts(self, chunk: Tuple[np.ndarray, np.ndarray], n: int) -> int:
+    def _stage_texts(self, chunk: Tuple[np.ndarray, np.ndarray], n: int, rows: Optional[int] = None) -> int:
         """The packed ``(text, offs)`` of ``n`` rows, through the pinned rows into slot 0, padded with empty
-        strings up to the bucket of ``n``, which is returned. The copies are asynchronous: the caller does
-        not overwrite the pinned rows (the next call) before something it waits for is ordered after them."""
+        strings up to the bucket of ``n`` (of ``rows >= n`` when given: a step that runs more rows than it
+        has texts), which is returned. The copies are asynchronous: the caller does not overwrite the pinned
+        rows (the next call) before something it waits for is ordered after them."""
         text, offs = chunk
         pin = self._pinned()
-        bk = self._bucket(n)
+        bk = self._bucket(n if rows is None else rows)
         pin["text"][:text.size].copy_(torch.from_numpy(text))
         pin["offs"][:n + 1].copy_(torch.from_numpy(offs))
         pin["offs"][n + 1:bk + 1].fill_(int(offs[-1]))  # padding rows: empty strings
@@ -1367,6 +1390,150 @@ class ClassifyEngine:
         scores = self.score_pairs(queries, passages, goff, max_query_tokens, label)
         return self.rank_scores(scores, goff, top_k, activation)
 
+    # ------------------------------------------------------ zero-shot classification (map_zero_shot)
+    # An NLI model reads every text with one hypothesis per candidate label as ``[CLS] text [SEP]
+    # hypothesis [SEP]`` (``ops.premise_assemble``). Neither segment is one row per pair: per chunk of at
+    # most B pairs the chunk's DISTINCT texts are staged and tokenized once in slot 0, its distinct
+    # hypotheses in the query slot of the re-ranker, and two index rows name each pair's text and
+    # hypothesis. One graph per bucket (two tokenizes, premise_assemble, model.nli_logits) and one D2D of
+    # the [m, 2] logits; after the last chunk one nli_rank launch and one D2H.
+    def _zero_shot_bufs(self) -> Dict[str, torch.Tensor]:
+        if getattr(self, "_zs", None) is None:
+            z = {"tidx": i32(self.B, device=self.device)}
+            if self.device.type == "cuda":
+                z["pin_tidx"] = i32(self.B, pin_memory=True)
+            self._zs = z
+        return self._zs
+
+    def _zero_shot_step(self, bucket: int, mh: int, ent: int, con: int) -> torch.Tensor:
+        """``(entailment, contradiction)`` logits ``[bucket, 2]`` of the staged pairs."""
+        r, z = self._rerank_bufs(), self._zero_shot_bufs()
+        cls_id, sep_id, pad_id = self._special_ids()
+        self._tokenize(r["text_q"], r["offs_q"], ids=r["ids_q"], lens=r["lens_q"], rows=bucket)
+        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+        ops.premise_assemble(self.ids_s[0][:bucket], self.lens_s[0][:bucket], r["ids_q"][:bucket], r["lens_q"][:bucket],
+                             z["tidx"], r["qidx"], mh, cls_id, sep_id, pad_id, ids=r["ids"], type_ids=r["type_ids"],
+                             lens=r["lens"], rows=bucket)
+        return self.model.nli_logits(r["ids"][:bucket], r["lens"][:bucket], r["type_ids"][:bucket], ent, con)
+
+    def _premise_chunks(self, texts: Sequence, hyps: Sequence, tid: np.ndarray, hid: np.ndarray, mh: int):
+        """The chunk staging of the premise pairs ``(tid[p], hid[p])``, a sibling of :meth:`_pair_chunks`:
+        yields ``(c0, m, bucket, rows)`` per chunk of at most ``B`` pairs. On the GPU the chunk's distinct
+        texts go through the pinned rows into slot 0, its distinct hypotheses into the query slot, the
+        pairs' local text / hypothesis indices into ``tidx`` / ``qidx`` (padding rows: text 0 with
+        hypothesis 0), ``rows`` is None and the caller runs its step on ``bucket`` rows; on the CPU ``rows``
+        is the assembled ``(ids, type_ids, lens)``."""
+        P = int(tid.size)
+        cuda = self.device.type == "cuda"
+        if P == 0:
+            return
+        r, z = self._rerank_bufs(), self._zero_shot_bufs()
+        free = None  # the event after which the pinned rows of the previous chunk may be overwritten
+        for c0 in range(0, P, self.B):
+            m = min(self.B, P - c0)
+            used_t, local_t = np.unique(tid[c0:c0 + m], return_inverse=True)  # at most m of either
+            used_h, local_h = np.unique(hid[c0:c0 + m], return_inverse=True)
+            text_t, offs_t = pack_rows(self._encode_rows([texts[int(t)] for t in used_t]))
+            text_h, offs_h = pack_rows(self._encode_rows([hyps[int(h)] for h in used_h]))
+            local_t, local_h = local_t.astype(np.int32), local_h.astype(np.int32)
+            if not cuda:
+                ids_t, lens_t = self._tokenize(torch.from_numpy(text_t), torch.from_numpy(offs_t))
+                ids_h, lens_h = self._tokenize(torch.from_numpy(text_h), torch.from_numpy(offs_h))
+                yield c0, m, None, ops.premise_assemble(ids_t, lens_t, ids_h, lens_h, torch.from_numpy(local_t),
+                                                        torch.from_numpy(local_h), mh, *self._special_ids())
+                continue
+            if free is not None:
+                free.synchronize()
+            bk, nh = self._stage_texts((text_t, offs_t), len(used_t), rows=m), len(used_h)
+            r["pin_text_q"][:text_h.size].copy_(torch.from_numpy(text_h))
+            r["pin_offs_q"][:nh + 1].copy_(torch.from_numpy(offs_h))
+            r["pin_offs_q"][nh + 1:bk + 1].fill_(int(offs_h[-1]))
+            r["pin_qidx"][:m].copy_(torch.from_numpy(local_h))
+            r["pin_qidx"][m:bk].zero_()  # padding rows: text 0 with hypothesis 0, their logits dropped
+            z["pin_tidx"][:m].copy_(torch.from_numpy(local_t))
+            z["pin_tidx"][m:bk].zero_()
+            if text_h.size:
+                r["text_q"][:text_h.size].copy_(r["pin_text_q"][:text_h.size], non_blocking=True)
+            r["offs_q"][:bk + 1].copy_(r["pin_offs_q"][:bk + 1], non_blocking=True)
+            r["qidx"][:bk].copy_(r["pin_qidx"][:bk], non_blocking=True)
+            z["tidx"][:bk].copy_(z["pin_tidx"][:bk], non_blocking=True)
+            free = torch.cuda.Event()
+            free.record()
+            yield c0, m, bk, None
+        if free is not None:
+            free.synchronize()  # the pinned rows are free for the next call, whichever form it is
+
+    def nli_ids(self, ent: Optional[int] = None, con: Optional[int] = None) -> Tuple[int, int]:
+        """The checked ``(entailment, contradiction)`` label ids; None: ``(num_labels - 1, 0)``."""
+        C = self.cfg.num_labels
+        ent = C - 1 if ent is None else ent
+        con = 0 if con is None else con
+        for v in (ent, con):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < C:
+                raise ValueError("ent and con must be ints in [0, num_labels)")
+        if ent == con:
+            raise ValueError("ent and con must be distinct")
+        return ent, con
+
+    def score_premises(self, texts: Sequence, hyps: Sequence, ranges: Sequence[Tuple[int, int]],
+                       max_hypothesis_tokens: Optional[int] = None, ent: Optional[int] = None,
+                       con: Optional[int] = None) -> torch.Tensor:
+        """NLI logits ``[P, 2]`` fp32 = (entailment, contradiction), left on the engine's device (a DP caller
+        all-gathers them): text ``t`` is read with each of the hypotheses ``hyps[ranges[t][0]:ranges[t][1]]``,
+        the pairs text-major. A pair's row is ``[CLS] text [SEP] hypothesis [SEP]`` (``ops.premise_assemble``):
+        the text gives way (HF ``only_first``), the hypothesis is kept up to ``max_hypothesis_tokens``
+        (default ``min(32, (S - 3) // 2)``; HF has no such cut)."""
+        if len(ranges) != len(texts):
+            raise ValueError("ranges must hold one (start, end) per text")
+        ranges = [(int(a), int(b)) for a, b in ranges]
+        if any(not 0 <= a <= b <= len(hyps) for a, b in ranges):
+            raise ValueError("ranges must lie in [0, len(hyps)] with start <= end")
+        if self.S < 4:
+            raise ValueError("score_premises needs seq_len >= 4")
+        mh = default_max_query_tokens(self.S) if max_hypothesis_tokens is None else max_hypothesis_tokens
+        if isinstance(mh, bool) or not isinstance(mh, int) or mh < 0:
+            raise ValueError("max_hypothesis_tokens must be an int >= 0")
+        ent, con = self.nli_ids(ent, con)
+        counts = np.asarray([b - a for a, b in ranges], dtype=np.int64)
+        tid = np.repeat(np.arange(len(texts), dtype=np.int64), counts)
+        hid = (np.concatenate([np.arange(a, b, dtype=np.int64) for a, b in ranges]) if len(ranges)
+               else np.zeros(0, dtype=np.int64))
+        P = int(tid.size)
+        pair = torch.empty((P, 2), dtype=torch.float32, device=self.device)
+        for c0, m, bk, rows in self._premise_chunks(texts, hyps, tid, hid, mh):
+            if rows is not None:
+                ids, types, lens = rows
+                pair[c0:c0 + m] = self.model.nli_logits(ids, lens, types, ent, con)
+            else:
+                out = self._replay(("zeroshot", bk, mh, ent, con), lambda: self._zero_shot_step(bk, mh, ent, con))
+                pair[c0:c0 + m].copy_(out[:m])
+        return pair
+
+    def rank_labels(self, pair: torch.Tensor, goff: Sequence[int], multi_label: bool = False) -> ZeroShotResult:
+        """Every text's labels scored and ranked in full from its NLI logits (``ops.nli_rank``): one launch
+        and one D2H, which also brings the raw logits to the host."""
+        if not isinstance(multi_label, bool):
+            raise ValueError("multi_label must be a bool")
+        P = int(pair.shape[0])
+        T = len(goff) - 1
+        goff = self._check_goff(goff, T, P)
+        if P == 0 or T == 0:
+            return ZeroShotResult(T, P, goff, torch.zeros(0, dtype=torch.int32), torch.zeros(0), pair.float().cpu())
+        pair = pair.contiguous()
+        order, score = ops.nli_rank(pair, torch.tensor(goff, dtype=torch.int32).to(pair.device), multi_label)
+        both = torch.cat([order.view(torch.float32), score, pair.reshape(-1)]).cpu()  # one D2H, one sync
+        return ZeroShotResult(T, P, goff, both[:P].clone().view(torch.int32), both[P:2 * P].clone(),
+                              both[2 * P:].clone().view(P, 2))
+
+    def zero_shot(self, texts: Sequence, hyps: Sequence, ranges: Sequence[Tuple[int, int]], multi_label: bool = False,
+                  max_hypothesis_tokens: Optional[int] = None, ent: Optional[int] = None,
+                  con: Optional[int] = None) -> ZeroShotResult:
+        """:meth:`score_premises`, then :meth:`rank_labels`."""
+        if not isinstance(multi_label, bool):
+            raise ValueError("multi_label must be a bool")
+        pair = self.score_premises(texts, hyps, ranges, max_hypothesis_tokens, ent, con)
+        return self.rank_labels(pair, _offsets([b - a for a, b in ranges]), multi_label)
+
     def memory_bytes(self) -> int:
         """Resident device bytes: weights, the LayerNorm-folded weight copies once built
         (they are ~45 % of the encoder weights), staging and token buffers."""
@@ -1389,6 +1556,8 @@ class ClassifyEngine:
         # windowed answer: the long passage rows, the window table and the [R, n] window-row buffers
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_wn", None) or {}).values() if t.is_cuda)
         extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_wr", None) or ()))
+        # zero-shot: the pairs' text index row (its other buffers are the re-ranker's)
+        extra += sum(t.numel() * t.element_size() for t in (getattr(self, "_zs", None) or {}).values() if t.is_cuda)
         return (self.pack.nbytes + extra + sum(t.numel() for t in self.text)
                 + sum(t.numel() * 4 for t in self.ids_s) + sum(t.numel() * 4 for t in self.offs))
 

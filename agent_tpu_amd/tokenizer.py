@@ -391,6 +391,57 @@ def pair_rows(ids_q: np.ndarray, lens_q: np.ndarray, ids_p: np.ndarray, lens_p: 
     return ids, types, lens
 
 
+def premise_rows(ids_t: np.ndarray, lens_t: np.ndarray, ids_h: np.ndarray, lens_h: np.ndarray, tidx: np.ndarray,
+                 hidx: np.ndarray, max_hypothesis_tokens: int, cls_id: int = CLS_ID, sep_id: int = SEP_ID,
+                 pad_id: int = PAD_ID) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """atpu-premise v1: NLI rows ``[CLS] text [SEP] hypothesis [SEP]`` assembled from the single-segment
+    rows either tokenizer emits; pure-Python twin of ``csrc/kernels/zeroshot.hip``
+    ``premise_assemble_kernel``, bit-for-bit. The opposite of :func:`pair_rows`: the long first segment
+    gives way, the short second one is kept, and neither is one row per pair.
+
+    For row ``r`` with ``t = clamp(tidx[r], 0, T - 1)``, ``h = clamp(hidx[r], 0, Hn - 1)``, ``S`` the row
+    width (>= 4):
+
+    * ``nh = min(clamp(lens_h[h], 2, S) - 2, max_hypothesis_tokens, S - 3)``;
+    * ``nt = min(clamp(lens_t[t], 2, S) - 2, S - 3 - nh)``;
+    * ``ids = [CLS] t_tok[0:nt] [SEP] h_tok[0:nh] [SEP]`` then ``[PAD]``;
+    * ``type_ids`` 1 on positions ``nt + 2 .. nt + nh + 2``, 0 elsewhere;
+    * ``len = nt + nh + 3``.
+
+    Where ``max_hypothesis_tokens`` does not cut the hypothesis this is HF ``BertTokenizer(text,
+    hypothesis, truncation="only_first", max_length=S, padding="max_length")``, under the caveats of
+    atpu-wordpiece v1. Returns ``(ids[P, S], type_ids[P, S], lens[P])``, all int32."""
+    ids_t, ids_h = np.asarray(ids_t, dtype=np.int32), np.asarray(ids_h, dtype=np.int32)
+    lens_t, lens_h = np.asarray(lens_t, dtype=np.int32), np.asarray(lens_h, dtype=np.int32)
+    tidx, hidx = np.asarray(tidx, dtype=np.int32), np.asarray(hidx, dtype=np.int32)
+    if ids_t.ndim != 2 or ids_h.ndim != 2 or ids_t.shape[1] != ids_h.shape[1]:
+        raise ValueError("premise_rows: ids_t [T, S] and ids_h [Hn, S]")
+    Tn, S = ids_t.shape
+    Hn = ids_h.shape[0]
+    mh = int(max_hypothesis_tokens)
+    if S < 4 or Tn < 1 or Hn < 1 or mh < 0:
+        raise ValueError("premise_rows: S >= 4, T >= 1, Hn >= 1 and max_hypothesis_tokens >= 0")
+    if lens_t.shape != (Tn,) or lens_h.shape != (Hn,) or tidx.ndim != 1 or hidx.shape != tidx.shape:
+        raise ValueError("premise_rows: lens_t [T], lens_h [Hn], tidx [P] and hidx [P]")
+    P = tidx.shape[0]
+    ids = np.full((P, S), pad_id, dtype=np.int32)
+    types = np.zeros((P, S), dtype=np.int32)
+    lens = np.zeros(P, dtype=np.int32)
+    for r in range(P):
+        t = min(max(int(tidx[r]), 0), Tn - 1)
+        h = min(max(int(hidx[r]), 0), Hn - 1)
+        nh = min(min(max(int(lens_h[h]), 2), S) - 2, mh, S - 3)
+        nt = min(min(max(int(lens_t[t]), 2), S) - 2, S - 3 - nh)
+        ids[r, 0] = cls_id
+        ids[r, 1:1 + nt] = ids_t[t, 1:1 + nt]
+        ids[r, 1 + nt] = sep_id
+        ids[r, 2 + nt:2 + nt + nh] = ids_h[h, 1:1 + nh]
+        ids[r, 2 + nt + nh] = sep_id
+        types[r, 2 + nt:3 + nt + nh] = 1
+        lens[r] = nt + nh + 3
+    return ids, types, lens
+
+
 # ---------------------------------------------------------------- atpu-window v1
 def window_table(T: int, nq: int, S: int, doc_stride: int) -> List[Tuple[int, int, int, int]]:
     """atpu-window v1: the windows ``(start, len, own_lo, own_hi)`` of a passage of ``T`` tokens read

@@ -30,6 +30,11 @@ default), ``pool_*`` / ``cls_*`` are optional, and ``map_classify`` / ``map_rera
 ``mlm_ln_b`` / ``mlm_out_b`` (the masked-LM head ``map_fill`` needs; the decoder is the word embeddings),
 ``pool_*`` / ``cls_*`` are optional, and the other head ops refuse it. ``?mlm=1`` on a preset adds a
 random-init MLM head.
+``?nli=1`` on a preset makes it an NLI classifier for ``map_zero_shot``: 3 labels unless ``labels=`` says otherwise,
+entailment id 2 and contradiction id 0 (the MNLI order). A classifier json may name its labels in
+``"nli_labels": [...]`` (one per label): the entailment id is the first name that starts with "entail", the
+contradiction id the last label if that is label 0, else label 0 (HF's rule). No new weights: the NLI head is
+the pooler and classifier.
 Random-init weights are seeded, so every rank/host builds identical weights;
 under DP rank 0 initialises and broadcasts them (RCCL).
 """
@@ -68,6 +73,9 @@ class ModelSpec:
     tag_names: Optional[Tuple[str, ...]] = None  # "tag_labels" of the json; None: ops.default_tag_names
     tag_outside: Tuple[str, ...] = ("O",)
     mlm: bool = False  # a masked-LM head ("?mlm=1", or "head": "mlm" in the json, which clears ``head``): map_fill
+    # an NLI classifier: (entailment_id, contradiction_id) ("?nli=1": (2, 0), or "nli_labels" in the json); None:
+    # map_zero_shot takes (num_labels - 1, 0) unless the payload names them
+    nli: Optional[Tuple[int, int]] = None
 
 
 def _flag(value: Any) -> bool:
@@ -83,6 +91,18 @@ def _tags(value: Any) -> int:
     return n
 
 
+def nli_ids_of(names: Any, num_labels: int, where: str) -> Tuple[int, int]:
+    """``(entailment_id, contradiction_id)`` from a model's label names: the first name that starts with
+    "entail" (any case) and, HF's own rule, the last label if that is label 0, else label 0."""
+    if (not isinstance(names, list) or len(names) != num_labels or num_labels < 2
+            or not all(isinstance(n, str) for n in names)):
+        raise ValueError(f'{where}: "nli_labels" must name each of the num_labels (>= 2) labels')
+    ent = next((i for i, n in enumerate(names) if n.strip().lower().startswith("entail")), None)
+    if ent is None:
+        raise ValueError(f'{where}: "nli_labels" has no label that starts with "entail"')
+    return ent, (num_labels - 1 if ent == 0 else 0)
+
+
 def parse_spec(path: str) -> ModelSpec:
     from agent_tpu_amd.models.bert import PRESETS, resolve_quant
 
@@ -95,11 +115,12 @@ def parse_spec(path: str) -> ModelSpec:
     vocab = q.get("vocab") or None
     lowercase = _flag(q["lowercase"]) if "lowercase" in q else None
     if base in PRESETS:
-        return ModelSpec(path, base, int(q.get("labels", os.getenv("CLASSIFY_NUM_LABELS", "2"))),
+        nli = _flag(q.get("nli", "0"))  # MNLI order: contradiction, neutral, entailment
+        return ModelSpec(path, base, int(q.get("labels", "3" if nli else os.getenv("CLASSIFY_NUM_LABELS", "2"))),
                          int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
                          vocab=vocab, lowercase=True if lowercase is None else lowercase,
                          qa=_flag(q.get("qa", "0")), tags=_tags(q.get("tags", "0")),
-                         mlm=_flag(q.get("mlm", "0")))
+                         mlm=_flag(q.get("mlm", "0")), nli=(2, 0) if nli else None)
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
@@ -118,10 +139,14 @@ def parse_spec(path: str) -> ModelSpec:
             _tags(len(names))
             names = tuple(names)
             outside = tuple(str(n) for n in meta.get("outside", ["O"]))
+        nli = None
+        if meta.get("nli_labels") is not None:
+            nli = nli_ids_of(meta["nli_labels"], int(meta.get("num_labels", 2)), base + ".json")
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
                          file=base, quant=quant, vocab=vocab, lowercase=lowercase,
                          head=head not in ("none", "qa", "token", "mlm"), qa=head == "qa",
-                         tags=len(names) if names else 0, tag_names=names, tag_outside=outside, mlm=head == "mlm")
+                         tags=len(names) if names else 0, tag_names=names, tag_outside=outside, mlm=head == "mlm",
+                         nli=nli)
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
