@@ -260,6 +260,47 @@ PYBIND11_MODULE(_atpu, m) {
       "merge of the per-split lists of sim_topk_partial in (value desc, row asc) order",
       py::arg("ws"), py::arg("scores"), py::arg("ids"), py::arg("nq"), py::arg("P"), py::arg("k"), py::arg("kk"),
       py::arg("id_base"), py::arg("stream"));
+  m.def("kmeans_shape_ok", &kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
+  m.def(
+      "kmeans_assign",
+      [](uintptr_t x, uintptr_t c, uintptr_t bias, uintptr_t prev_labels, uintptr_t labels, uintptr_t best,
+         uintptr_t changed, int N, int K, int D, int max_wgs, uintptr_t stream) {
+        kmeans_assign(P<const float>(x), P<const float>(c), P<const float>(bias), P<const int32_t>(prev_labels),
+                      P<int32_t>(labels), P<float>(best), P<int64_t>(changed), N, K, D, max_wgs, S(stream));
+      },
+      "k-means assignment: arg-max of dot(x, c) (+ bias, 0 = none) per row in sim_topk's arithmetic, and the count of "
+      "changed labels",
+      py::arg("x"), py::arg("c"), py::arg("bias"), py::arg("prev_labels"), py::arg("labels"), py::arg("best"),
+      py::arg("changed"), py::arg("N"), py::arg("K"), py::arg("D"), py::arg("max_wgs"), py::arg("stream"));
+  m.def(
+      "fixed_sum",
+      [](uintptr_t v, int64_t n, int shift, uintptr_t out, uintptr_t stream) {
+        fixed_sum(P<const float>(v), n, shift, P<int64_t>(out), S(stream));
+      },
+      "order-free int64 sum of rint(v * 2^shift)", py::arg("v"), py::arg("n"), py::arg("shift"), py::arg("out"),
+      py::arg("stream"));
+  m.def("kmeans_update_ws_bytes", &kmeans_update_ws_bytes, "workspace bytes of kmeans_update", py::arg("N"),
+        py::arg("K"));
+  m.def(
+      "kmeans_update",
+      [](uintptr_t x, uintptr_t labels, int shift, uintptr_t sums, uintptr_t counts, uintptr_t ws, int N, int K, int D,
+         uintptr_t stream) {
+        kmeans_update(P<const float>(x), P<const int32_t>(labels), shift, P<int64_t>(sums), P<int64_t>(counts),
+                      P<int32_t>(ws), N, K, D, S(stream));
+      },
+      "k-means update: per-label int64 fixed-point sums [K, D] and member counts [K]", py::arg("x"), py::arg("labels"),
+      py::arg("shift"), py::arg("sums"), py::arg("counts"), py::arg("ws"), py::arg("N"), py::arg("K"), py::arg("D"),
+      py::arg("stream"));
+  m.def(
+      "kmeans_finalize",
+      [](uintptr_t sums, uintptr_t counts, uintptr_t c_old, uintptr_t c_new, uintptr_t bias, int K, int D, int shift,
+         int cosine, uintptr_t stream) {
+        kmeans_finalize(P<const int64_t>(sums), P<const int64_t>(counts), P<const float>(c_old), P<float>(c_new),
+                        P<float>(bias), K, D, shift, cosine, S(stream));
+      },
+      "k-means finalize: means of the fixed-point sums (normalised for cosine), empty clusters kept, bias for l2",
+      py::arg("sums"), py::arg("counts"), py::arg("c_old"), py::arg("c_new"), py::arg("bias"), py::arg("K"),
+      py::arg("D"), py::arg("shift"), py::arg("cosine"), py::arg("stream"));
   m.def("decode_attention", [](uintptr_t q, int ldq, uintptr_t k, uintptr_t v, int ldkv, int seq_stride, int group,
                                uintptr_t lens, uintptr_t step_dev, uintptr_t hist, int hist_stride, uintptr_t bias,
                                int bias_stride, uintptr_t out, int ldo, int rows, int H, float scale, uintptr_t stream,

@@ -158,6 +158,30 @@ void sim_topk_merge(const float* ws, float* scores, int64_t* ids, int nq, int P,
 void sim_topk_partial_f16(const float* q, const _Float16* c, const float* row_scale, float* ws, int nq, int N, int D,
                           int k, int P, hipStream_t stream);
 
+// ---------------------------------------------------------------- k-means (kmeans.hip)
+// Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)
+// in the order of better() (score desc, centroid asc), best[i] that score; every score is one fp32
+// accumulator fed in sim_topk's column order, so without a bias (labels, best) equal sim_topk(x, c, 1)
+// bit for bit, whatever the launch shape. *changed (int64, zeroed here) counts labels[i] != prev_labels[i].
+// D % 64 == 0, D in [64, 1024], K in [1, kKmeansMaxK], N in [1, 2^31 - 256]. max_wgs: a cap on the
+// persistent grid (0: the device's own), for tests. Nothing outside the tensors is read.
+constexpr int kKmeansMaxK = 4096;
+bool kmeans_shape_ok(int D, int K);
+void kmeans_assign(const float* x, const float* c, const float* bias, const int32_t* prev_labels, int32_t* labels,
+                   float* best, int64_t* changed, int N, int K, int D, int max_wgs, hipStream_t stream);
+// Order-free sum: *out = sum_i rint(v[i] * 2^shift) as int64 (ties to even; integer adds, any order).
+void fixed_sum(const float* v, int64_t n, int shift, int64_t* out, hipStream_t stream);
+// Centroid update: sums[k, d] = sum over labels[i] == k of rint(x[i, d] * 2^shift), counts[k] = members
+// (both int64, zeroed here; a label outside [0, K) leaves its row out). ws: kmeans_update_ws_bytes(N, K).
+size_t kmeans_update_ws_bytes(int N, int K);
+void kmeans_update(const float* x, const int32_t* labels, int shift, int64_t* sums, int64_t* counts, int32_t* ws,
+                   int N, int K, int D, hipStream_t stream);
+// New centroids: for counts[k] > 0 the mean float(double(sum) / (double(count) * 2^shift)), divided by
+// max(its fp64 norm, 1e-12) when cosine; an empty cluster keeps c_old[k]. bias (or nullptr)
+// = float(-0.5 * ||c_new[k]||^2). fp64, one rounding per operation, columns ascending. c_new may be c_old.
+void kmeans_finalize(const int64_t* sums, const int64_t* counts, const float* c_old, float* c_new, float* bias, int K,
+                     int D, int shift, int cosine, hipStream_t stream);
+
 // ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
 // Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),
 // q[r][k] = clamp(rint(x[r][k] * (127 / amax_r)), -127, 127). One wave per row; K % 16 == 0,

@@ -16,7 +16,8 @@ Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
 ``risk_accumulate`` (C3 all-reduce of {count,sum,min,max}),
 ``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
 tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
-per-rank top-k lists, merged on rank 0) and, from the :data:`BATCHED_OPS`
+per-rank top-k lists, merged on rank 0), ``map_cluster`` (C3 integer
+all-reduce of the centroid sums per iteration) and, from the :data:`BATCHED_OPS`
 table, the ``map_rerank``, ``map_answer``, ``map_tag``, ``map_fill`` and
 ``map_zero_shot`` tasks with their ``_batch`` forms (C2 all-gather of pair
 scores, span rows, entity records, mask candidates or NLI logits, ranked or
@@ -564,6 +565,18 @@ def search_batch_task(payload: Dict[str, Any]) -> Any:
 
     rank, ws = world()
     return ms.search_batch(payload["payloads"], rank, ws)
+
+
+# -------------------------------------------------------------- map_cluster
+@dp_task("map_cluster")
+def cluster_task(payload: Dict[str, Any]) -> Any:
+    """One map_cluster job: every rank holds its ``split_range`` slice of the rows; each k-means iteration
+    all-reduces the int64 centroid sums, counts and changed count (C3, SUM), so the result has the same bits
+    for every world size; the labels are all-gathered (C2) to rank 0 (:func:`ops.map_cluster.cluster_one`)."""
+    from ops import map_cluster as mc
+
+    rank, ws = world()
+    return mc.cluster_one(payload, rank, ws)
 
 
 # ---------------------------- map_rerank, map_answer, map_tag, map_fill, map_zero_shot
