@@ -301,6 +301,29 @@ PYBIND11_MODULE(_atpu, m) {
       "k-means finalize: means of the fixed-point sums (normalised for cosine), empty clusters kept, bias for l2",
       py::arg("sums"), py::arg("counts"), py::arg("c_old"), py::arg("c_new"), py::arg("bias"), py::arg("K"),
       py::arg("D"), py::arg("shift"), py::arg("cosine"), py::arg("stream"));
+  m.def("sim_join_ok", &sim_join_ok, "the D that sim_join takes", py::arg("D"));
+  m.def(
+      "sim_join",
+      [](uintptr_t x, uintptr_t y, float threshold, int Nx, int Ny, int D, int x_base, int y_base, uintptr_t pairs,
+         uintptr_t scores, uintptr_t count, int64_t cap, int max_wgs, int panel_steps, uintptr_t stream) {
+        sim_join(P<const float>(x), P<const float>(y), threshold, Nx, Ny, D, x_base, y_base, P<int32_t>(pairs),
+                 P<float>(scores), P<int64_t>(count), cap, max_wgs, panel_steps, S(stream));
+      },
+      "similarity join: the pairs (x_base + i < y_base + j) with dot(x[i], y[j]) >= threshold in sim_topk's "
+      "arithmetic, at most cap of them stored, the true total in count",
+      py::arg("x"), py::arg("y"), py::arg("threshold"), py::arg("Nx"), py::arg("Ny"), py::arg("D"), py::arg("x_base"),
+      py::arg("y_base"), py::arg("pairs"), py::arg("scores"), py::arg("count"), py::arg("cap"), py::arg("max_wgs"),
+      py::arg("panel_steps"), py::arg("stream"));
+  m.def(
+      "cc_init", [](uintptr_t parent, int N, uintptr_t stream) { cc_init(P<int32_t>(parent), N, S(stream)); },
+      "connected components: parent[v] = v", py::arg("parent"), py::arg("N"), py::arg("stream"));
+  m.def(
+      "cc_round",
+      [](uintptr_t pairs, int64_t E, uintptr_t parent, int N, uintptr_t changed, uintptr_t stream) {
+        cc_round(P<const int32_t>(pairs), E, P<int32_t>(parent), N, P<int32_t>(changed), S(stream));
+      },
+      "connected components: one round of atomicMin hooks over the edges and a full compression",
+      py::arg("pairs"), py::arg("E"), py::arg("parent"), py::arg("N"), py::arg("changed"), py::arg("stream"));
   m.def("decode_attention", [](uintptr_t q, int ldq, uintptr_t k, uintptr_t v, int ldkv, int seq_stride, int group,
                                uintptr_t lens, uintptr_t step_dev, uintptr_t hist, int hist_stride, uintptr_t bias,
                                int bias_stride, uintptr_t out, int ldo, int rows, int H, float scale, uintptr_t stream,

@@ -182,6 +182,26 @@ void kmeans_update(const float* x, const int32_t* labels, int shift, int64_t* su
 void kmeans_finalize(const int64_t* sums, const int64_t* counts, const float* c_old, float* c_new, float* bias, int K,
                      int D, int shift, int cosine, hipStream_t stream);
 
+// ---------------------------------------------------------------- near-duplicates (sim_join.hip)
+// Similarity join: every pair (I, J) = (x_base + i, y_base + j) with I < J and dot(x[i], y[j]) >= threshold
+// (an fp32 compare; the score is one fp32 accumulator fed in sim_topk's column order, so it has sim_topk's
+// bits whatever the launch shape) goes to pairs [cap, 2] / scores [cap] in arbitrary order. *count (int64,
+// zeroed here) ends as the true total, also beyond cap; nothing is written at or past cap. D % 64 == 0,
+// D in [64, 1024]; every id in [0, 2^31 - 256). max_wgs caps the persistent grid and panel_steps sets the
+// 32-row steps of y per work item (0: the defaults); the emitted set depends on neither. Nothing outside
+// x[0:Nx] and y[0:Ny] is read.
+bool sim_join_ok(int D);
+void sim_join(const float* x, const float* y, float threshold, int Nx, int Ny, int D, int x_base, int y_base,
+              int32_t* pairs, float* scores, int64_t* count, int64_t cap, int max_wgs, int panel_steps,
+              hipStream_t stream);
+// Connected components by minimum label: cc_init sets parent[v] = v; cc_round hooks every edge of
+// pairs [E, 2] (atomicMin, parent[v] <= v always) and compresses every node to its root, and leaves
+// *changed (int32, zeroed here) != 0 when a hook lowered a parent. The caller repeats rounds until one
+// changes nothing; parent then holds every node's smallest component member. Edges with an endpoint
+// outside [0, N) are skipped.
+void cc_init(int32_t* parent, int N, hipStream_t stream);
+void cc_round(const int32_t* pairs, int64_t E, int32_t* parent, int N, int32_t* changed, hipStream_t stream);
+
 // ---------------------------------------------------------------- INT8 GEMM (gemm_i8.hip)
 // Symmetric per-row quantisation, 127 levels: scale[r] = amax_r / 127 (1 for an all-zero row),
 // q[r][k] = clamp(rint(x[r][k] * (127 / amax_r)), -127, 127). One wave per row; K % 16 == 0,

@@ -22,6 +22,8 @@ from .pool import pool_embed, pool_embed_ok, pool_embed_ref  # noqa: F401
 from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
 from .cluster import (kmeans_assign, kmeans_assign_ref, kmeans_update, kmeans_update_ref, kmeans_finalize,  # noqa: F401
                       kmeans_finalize_ref, fixed_shift, fixed_sum, fixed_sum_ref, kmeans_ok)
+from .dedup import (sim_join, sim_join_ok, sim_join_ref, sort_pairs, cc_min_labels,  # noqa: F401
+                    cc_min_labels_ref)
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .rerank import pair_assemble, pair_assemble_ref, group_topk, group_topk_ref  # noqa: F401

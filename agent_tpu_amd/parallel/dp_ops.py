@@ -17,7 +17,8 @@ Registered bodies: ``map_classify_csv`` (C2 all-gather of top-k),
 ``map_summarize`` (C5 all-gather of generated token ids), the ``map_embed_*``
 tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
 per-rank top-k lists, merged on rank 0), ``map_cluster`` (C3 integer
-all-reduce of the centroid sums per iteration) and, from the :data:`BATCHED_OPS`
+all-reduce of the centroid sums per iteration), ``map_dedup`` (C2 ragged
+all-gather of the join's pairs) and, from the :data:`BATCHED_OPS`
 table, the ``map_rerank``, ``map_answer``, ``map_tag``, ``map_fill`` and
 ``map_zero_shot`` tasks with their ``_batch`` forms (C2 all-gather of pair
 scores, span rows, entity records, mask candidates or NLI logits, ranked or
@@ -577,6 +578,18 @@ def cluster_task(payload: Dict[str, Any]) -> Any:
 
     rank, ws = world()
     return mc.cluster_one(payload, rank, ws)
+
+
+# ---------------------------------------------------------------- map_dedup
+@dp_task("map_dedup")
+def dedup_task(payload: Dict[str, Any]) -> Any:
+    """One map_dedup job: every rank holds all rows and joins the row blocks ``b = rank (mod ws)`` against them;
+    the pairs are ragged-all-gathered (C2) to every rank and sorted, so the groups have the same bits for
+    every world size (:func:`ops.map_dedup.dedup_one`)."""
+    from ops import map_dedup as md
+
+    rank, ws = world()
+    return md.dedup_one(payload, rank, ws)
 
 
 # ---------------------------- map_rerank, map_answer, map_tag, map_fill, map_zero_shot

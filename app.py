@@ -246,7 +246,7 @@ METRICS = Metrics()
 
 
 # --------------------------------------------------------------- profile
-GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_cluster", "map_rerank", "map_answer", "map_tag", "map_fill",
+GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_cluster", "map_dedup", "map_rerank", "map_answer", "map_tag", "map_fill",
            "map_zero_shot", "map_summarize", "risk_accumulate"}
 BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag", "map_fill",
              "map_zero_shot", "map_summarize"}

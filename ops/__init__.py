@@ -57,6 +57,7 @@ OP_TO_MODULE: Dict[str, str] = {
     "map_embed": "map_embed",
     "map_search": "map_search",
     "map_cluster": "map_cluster",
+    "map_dedup": "map_dedup",
     "map_rerank": "map_rerank",
     "map_answer": "map_answer",
     "map_tag": "map_tag",
