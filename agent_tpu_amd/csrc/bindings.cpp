@@ -251,6 +251,50 @@ PYBIND11_MODULE(_atpu, m) {
       "sim_topk_partial over a float16 corpus, the fp32 score times row_scale [N] (0 = none) before the ranking",
       py::arg("q"), py::arg("c"), py::arg("row_scale"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"),
       py::arg("k"), py::arg("P"), py::arg("stream"));
+  m.def("sim_topk_splits_live", &sim_topk_splits_live,
+        "the split count the masked sim_topk kernels run for a wanted one, from the live-step count", py::arg("n_live"),
+        py::arg("want"));
+  m.def(
+      "sim_topk_partial_masked",
+      [](uintptr_t q, uintptr_t c, uintptr_t words, uintptr_t live, uintptr_t ws, int nq, int N, int D, int k,
+         int splits, int n_live, uintptr_t stream) {
+        sim_topk_partial_masked(P<const float>(q), P<const float>(c), P<const int32_t>(words), P<const int32_t>(live),
+                                P<float>(ws), nq, N, D, k, splits, n_live, S(stream));
+      },
+      "sim_topk_partial over the rows whose bit is set in words [ceil(N / 32)], walking the live words only",
+      py::arg("q"), py::arg("c"), py::arg("words"), py::arg("live"), py::arg("ws"), py::arg("nq"), py::arg("N"),
+      py::arg("D"), py::arg("k"), py::arg("P"), py::arg("n_live"), py::arg("stream"));
+  m.def(
+      "sim_topk_partial_masked_f16",
+      [](uintptr_t q, uintptr_t c, uintptr_t row_scale, uintptr_t words, uintptr_t live, uintptr_t ws, int nq, int N,
+         int D, int k, int splits, int n_live, uintptr_t stream) {
+        sim_topk_partial_masked_f16(P<const float>(q), P<const _Float16>(c), P<const float>(row_scale),
+                                    P<const int32_t>(words), P<const int32_t>(live), P<float>(ws), nq, N, D, k, splits,
+                                    n_live, S(stream));
+      },
+      "sim_topk_partial_masked over a float16 corpus, the fp32 score times row_scale [N] (0 = none)",
+      py::arg("q"), py::arg("c"), py::arg("row_scale"), py::arg("words"), py::arg("live"), py::arg("ws"),
+      py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("k"), py::arg("P"), py::arg("n_live"), py::arg("stream"));
+  m.def(
+      "row_mask_from_ids",
+      [](uintptr_t ids, int64_t m, int64_t base, int N, bool exclude, uintptr_t words, uintptr_t count,
+         uintptr_t stream) {
+        row_mask_from_ids(P<const int64_t>(ids), m, base, N, exclude ? 1 : 0, P<int32_t>(words), P<int64_t>(count),
+                          S(stream));
+      },
+      "row mask words [ceil(N / 32)] with the bit of every id in [base, base + N) set (exclude: cleared), and the count",
+      py::arg("ids"), py::arg("m"), py::arg("base"), py::arg("N"), py::arg("exclude"), py::arg("words"),
+      py::arg("count"), py::arg("stream"));
+  m.def(
+      "row_mask_from_labels",
+      [](uintptr_t labels, int N, uintptr_t values, int m, int64_t lo, int64_t hi, uintptr_t words, uintptr_t count,
+         uintptr_t stream) {
+        row_mask_from_labels(P<const int64_t>(labels), N, P<const int64_t>(values), m, lo, hi, P<int32_t>(words),
+                             P<int64_t>(count), S(stream));
+      },
+      "row mask of the rows whose label is one of the sorted values [m] (0 = none: lo <= label <= hi), and the count",
+      py::arg("labels"), py::arg("N"), py::arg("values"), py::arg("m"), py::arg("lo"), py::arg("hi"),
+      py::arg("words"), py::arg("count"), py::arg("stream"));
   m.def(
       "sim_topk_merge",
       [](uintptr_t ws, uintptr_t scores, uintptr_t ids, int nq, int splits, int k, int kk, int64_t id_base,

@@ -157,6 +157,28 @@ void sim_topk_merge(const float* ws, float* scores, int64_t* ids, int nq, int P,
 // Nothing outside c[0:N] and row_scale[0:N] is read.
 void sim_topk_partial_f16(const float* q, const _Float16* c, const float* row_scale, float* ws, int nq, int N, int D,
                           int k, int P, hipStream_t stream);
+// Filtered forms (sim_topk_masked.hip): only the rows whose bit is set in words [ceil(N / 32)] int32
+// (bit b of word w = row 32 w + b; bits at or past N are ignored) enter the lists; live [n_live]
+// int32 lists the non-zero words in ascending order, and only those 32-row steps are read. A score
+// has the bits of the unmasked kernel for the same (q, row), so the result equals sim_topk over the
+// gathered allowed rows with the ids mapped back. P = sim_topk_splits_live(n_live, wanted); the
+// workspace and sim_topk_merge are the same (kk <= the count of allowed rows is the caller's).
+// Nothing outside c[0:N], row_scale[0:N], words[0:ceil(N/32)] and live[0:n_live] is read.
+int sim_topk_splits_live(int n_live, int want);
+void sim_topk_partial_masked(const float* q, const float* c, const int32_t* words, const int32_t* live, float* ws,
+                             int nq, int N, int D, int k, int P, int n_live, hipStream_t stream);
+void sim_topk_partial_masked_f16(const float* q, const _Float16* c, const float* row_scale, const int32_t* words,
+                                 const int32_t* live, float* ws, int nq, int N, int D, int k, int P, int n_live,
+                                 hipStream_t stream);
+// Row-mask builders (sim_topk_masked.hip): words [ceil(N / 32)] and *count (int64, the set bits) are
+// written whole. from_ids: the bit of every id in [base, base + N) (duplicates and other ids are
+// harmless); exclude inverts, with the tail bits at or past N cleared. from_labels: rows whose label
+// is one of values [m <= kRowMaskMaxValues] (sorted ascending), or with values == nullptr in [lo, hi].
+constexpr int kRowMaskMaxValues = 256;
+void row_mask_from_ids(const int64_t* ids, int64_t m, int64_t base, int N, int exclude, int32_t* words,
+                       int64_t* count, hipStream_t stream);
+void row_mask_from_labels(const int64_t* labels, int N, const int64_t* values, int m, int64_t lo, int64_t hi,
+                          int32_t* words, int64_t* count, hipStream_t stream);
 
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)

@@ -22,10 +22,18 @@ accumulator once, before the ranking:
     scores[i, j] = dot(q[i], float(c[r])) * row_scale[r],   r = ids[i, j] - id_base
 
 which is cosine similarity over rows stored as they are (``row_scale = 1 / ||c[r]||``).
+
+A :class:`RowMask` (``csrc/kernels/sim_topk_masked.hip``) restricts the search to the rows whose
+bit is set: ``words [ceil(N / 32)]`` int32, bit ``b`` of word ``w`` = row ``32 w + b``, one word per
+32-row wave step of the kernel; ``live`` lists the non-zero words, and only those steps are read.
+The filter sits in the kernel's epilogue, and a score keeps the bits it has without a mask, so
+``sim_topk(q, c, k, mask=m)`` equals ``sim_topk(q, c[rows], k)`` over the allowed rows with the ids
+mapped back, bit for bit, at ``kk = min(k, m.count)`` columns. :func:`row_mask_from_ids` and
+:func:`row_mask_from_labels` build masks on the device (``*_ref``: their PyTorch twins).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -42,10 +50,140 @@ def sim_topk_ok(D: int, k: int) -> bool:
     return D % 64 == 0 and 64 <= D <= 1024 and 1 <= k <= MAX_K
 
 
+class RowMask(NamedTuple):
+    """The rows a filtered ``sim_topk`` may return (the module docstring has the layout)."""
+    words: torch.Tensor  # [ceil(rows / 32)] int32: bit b of word w = row 32 w + b; bits at or past rows are ignored
+    live: torch.Tensor  # int32: the indices of the non-zero words, ascending
+    rows: int  # N of the corpus slice the mask is for
+    count: int  # set bits below rows
+
+
+def mask_words(rows: int) -> int:
+    return (rows + 31) // 32
+
+
+def _finish_mask(words: torch.Tensor, rows: int, count: int) -> RowMask:
+    live = torch.nonzero(words).flatten().to(torch.int32)  # plumbing: once per mask
+    return RowMask(words, live, int(rows), int(count))
+
+
+def row_mask_bits(mask: RowMask) -> torch.Tensor:
+    """bool ``[rows]`` of the mask's words (on their device)."""
+    sh = torch.arange(32, device=mask.words.device, dtype=torch.int32)
+    return ((mask.words[:, None] >> sh) & 1).flatten()[:mask.rows].bool()
+
+
+def row_mask_from_bits(bits: torch.Tensor) -> RowMask:
+    """The mask of a bool ``[N]`` tensor, packed with PyTorch on its device (tests, benches, CPU)."""
+    check(bits.dim() == 1 and bits.dtype == torch.bool and bits.numel() >= 1, "row_mask: bits must be a bool [N]")
+    N = bits.numel()
+    b = torch.zeros(mask_words(N) * 32, dtype=torch.int64, device=bits.device)
+    b[:N] = bits
+    w = (b.view(-1, 32) << torch.arange(32, device=bits.device)).sum(1)  # < 2^32
+    words = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    return _finish_mask(words, N, int(bits.sum()))
+
+
+def _ids_tensor(ids, device) -> torch.Tensor:
+    t = ids if isinstance(ids, torch.Tensor) else torch.tensor(list(ids), dtype=torch.int64)
+    check(t.dim() == 1 and t.dtype == torch.int64, "row_mask_from_ids: ids must be a 1-D int64 tensor or a list of ints")
+    return t.to(device).contiguous()
+
+
+def row_mask_from_ids_ref(ids: Union[torch.Tensor, Sequence[int]], N: int, base: int = 0, exclude: bool = False,
+                          device: Union[str, torch.device] = "cpu") -> RowMask:
+    """PyTorch twin of :func:`row_mask_from_ids`."""
+    check(isinstance(N, int) and 1 <= N <= MAX_ROWS, "row_mask_from_ids: N must be in [1, 2^31 - 256]")
+    t = _ids_tensor(ids, torch.device(device))
+    bits = torch.zeros(N, dtype=torch.bool, device=t.device)
+    t = t[(t >= base) & (t < base + N)] - base
+    bits[t] = True
+    return row_mask_from_bits(~bits if exclude else bits)
+
+
+def row_mask_from_ids(ids: Union[torch.Tensor, Sequence[int]], N: int, base: int = 0, exclude: bool = False,
+                      device: Union[str, torch.device, None] = None) -> RowMask:
+    """The mask of a slice of ``N`` rows that starts at corpus row ``base``: the rows ``id - base`` of the
+    ``ids`` in ``[base, base + N)`` (duplicates and other slices' ids are skipped), or with ``exclude``
+    every other row. ``device`` defaults to the ids tensor's (CPU for a list)."""
+    check(isinstance(N, int) and 1 <= N <= MAX_ROWS, "row_mask_from_ids: N must be in [1, 2^31 - 256]")
+    check(isinstance(base, int) and 0 <= base < 2 ** 62, "row_mask_from_ids: base must be in [0, 2^62)")
+    dev = torch.device(device) if device is not None else (ids.device if isinstance(ids, torch.Tensor)
+                                                          else torch.device("cpu"))
+    if dev.type != "cuda":
+        return row_mask_from_ids_ref(ids, N, base, exclude, dev)
+    t = _ids_tensor(ids, dev)
+    words = torch.empty(mask_words(N), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    native().row_mask_from_ids(ptr(t) if t.numel() else 0, t.numel(), int(base), N, bool(exclude), ptr(words),
+                               ptr(count), launch_stream(words))
+    return _finish_mask(words, N, int(count.item()))
+
+
+def _label_args(labels, values, lo, hi):
+    check(isinstance(labels, torch.Tensor) and labels.dim() == 1 and labels.dtype == torch.int64
+          and 1 <= labels.numel() <= MAX_ROWS and labels.is_contiguous(),
+          "row_mask_from_labels: labels must be a contiguous 1-D int64 tensor of 1 .. 2^31 - 256 rows")
+    check((values is None) != (lo is None and hi is None) and (lo is None) == (hi is None),
+          "row_mask_from_labels: give values, or lo and hi")
+    i64 = lambda x: isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63  # noqa: E731
+    if values is not None:
+        vals = sorted(set(values.tolist() if isinstance(values, torch.Tensor) else values))
+        check(1 <= len(vals) <= 256 and all(i64(v) for v in vals), "row_mask_from_labels: 1 to 256 int64 values")
+        return vals, 0, 0
+    check(i64(lo) and i64(hi), "row_mask_from_labels: lo and hi must be int64 integers")
+    return None, lo, hi
+
+
+def row_mask_from_labels_ref(labels: torch.Tensor, values=None, lo: Optional[int] = None,
+                             hi: Optional[int] = None) -> RowMask:
+    """PyTorch twin of :func:`row_mask_from_labels`."""
+    vals, lo, hi = _label_args(labels, values, lo, hi)
+    if vals is not None:
+        bits = torch.isin(labels, torch.tensor(vals, dtype=torch.int64, device=labels.device))
+    else:
+        bits = (labels >= lo) & (labels <= hi)
+    return row_mask_from_bits(bits)
+
+
+def row_mask_from_labels(labels: torch.Tensor, values=None, lo: Optional[int] = None,
+                         hi: Optional[int] = None) -> RowMask:
+    """The mask of the rows whose int64 label is one of ``values`` (1 to 256 of them), or lies in
+    ``[lo, hi]`` (both inclusive), on the labels' device."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+        return row_mask_from_labels_ref(labels, values, lo, hi)
+    vals, lo, hi = _label_args(labels, values, lo, hi)
+    N = labels.numel()
+    words = torch.empty(mask_words(N), dtype=torch.int32, device=labels.device)
+    count = torch.empty(1, dtype=torch.int64, device=labels.device)
+    vt = torch.tensor(vals, dtype=torch.int64).to(labels.device) if vals is not None else None
+    native().row_mask_from_labels(ptr(labels), N, ptr(vt) if vt is not None else 0, len(vals) if vals else 0, lo, hi,
+                                  ptr(words), ptr(count), launch_stream(labels))
+    return _finish_mask(words, N, int(count.item()))
+
+
+def _check_mask(mask: RowMask, c: torch.Tensor) -> None:
+    N = c.shape[0]
+    check(isinstance(mask, RowMask), "sim_topk: mask must be a RowMask")
+    check(isinstance(mask.rows, int) and mask.rows == N, "sim_topk: the mask is for another number of rows")
+    check(isinstance(mask.words, torch.Tensor) and mask.words.dtype == torch.int32
+          and mask.words.shape == (mask_words(N),) and mask.words.is_contiguous(),
+          "sim_topk: mask.words must be a contiguous int32 [ceil(N / 32)]")
+    check(isinstance(mask.live, torch.Tensor) and mask.live.dtype == torch.int32 and mask.live.dim() == 1
+          and mask.live.numel() <= mask_words(N) and mask.live.is_contiguous(),
+          "sim_topk: mask.live must be a contiguous int32 list of at most ceil(N / 32) words")
+    check(isinstance(mask.count, int) and not isinstance(mask.count, bool) and 0 <= mask.count <= N
+          and (mask.count == 0) == (mask.live.numel() == 0), "sim_topk: mask.count must be the number of allowed rows")
+    same_device(c, mask.words)
+    same_device(c, mask.live)
+
+
 def sim_topk_ref(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, dtype=torch.float32,
-                 row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 row_scale: Optional[torch.Tensor] = None, mask: Optional[RowMask] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """PyTorch twin in ``dtype`` math -> (scores ``[nq, kk]`` of ``dtype``, ids ``[nq, kk]`` int64); also the
-    CPU path. Two stable sorts give the (score desc, id asc) order: ``torch.topk`` promises no tie order."""
+    CPU path. Two stable sorts give the (score desc, id asc) order: ``torch.topk`` promises no tie order.
+    With a ``mask`` the scores of the other rows are ``-inf`` before the sorts and ``kk = min(k, mask.count)``."""
     check(q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1], "sim_topk: q [nq, D] and c [N, D]")
     check(k >= 1 and c.shape[0] >= 1, "sim_topk: k and N must be >= 1")
     N = c.shape[0]
@@ -54,6 +192,10 @@ def sim_topk_ref(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, dty
     if row_scale is not None:
         check(row_scale.shape == (N,), "sim_topk: row_scale must be [N]")
         s = s * row_scale.to(dtype)
+    if mask is not None:
+        _check_mask(mask, c)
+        kk = min(k, mask.count)
+        s = s.masked_fill(~row_mask_bits(mask), float("-inf"))  # by select: a NaN in a masked row cannot leak
     order = torch.sort(s + 0.0, dim=1, descending=True, stable=True).indices[:, :kk]  # -0.0 + 0.0 = +0.0: they tie
     return torch.gather(s, 1, order), order.to(torch.int64) + int(id_base)
 
@@ -65,10 +207,12 @@ def auto_splits(N: int, nq: int, device: torch.device) -> int:
 
 
 def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits: Optional[int] = None,
-             row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             row_scale: Optional[torch.Tensor] = None, mask: Optional[RowMask] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(scores ``[nq, kk]`` fp32, ids ``[nq, kk]`` int64), ``kk = min(k, N)``, of the contiguous fp32
     ``q [nq, D]`` against the contiguous fp32 or fp16 ``c [N, D]``; ``row_scale`` (fp32 ``[N]``,
-    contiguous) goes with an fp16 ``c`` only."""
+    contiguous) goes with an fp16 ``c`` only. With a ``mask`` (on ``c``'s device) only its rows are
+    searched and ``kk = min(k, mask.count)``; a mask that allows nothing gives ``[nq, 0]`` without a launch."""
     check(q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1], "sim_topk: q [nq, D] and c [N, D]")
     check(q.dtype == torch.float32 and c.dtype in (torch.float32, torch.float16),
           "sim_topk: q must be fp32 and c fp32 or fp16")
@@ -89,12 +233,30 @@ def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits:
           f"sim_topk: splits must be in [1, {MAX_SPLITS}]")
     same_device(q, c)
     kk = min(k, N)
-    if nq == 0:
-        return (torch.empty((0, kk), dtype=torch.float32, device=q.device),
-                torch.empty((0, kk), dtype=torch.int64, device=q.device))
+    if mask is not None:
+        _check_mask(mask, c)
+        kk = min(k, mask.count)
+    if nq == 0 or kk == 0:
+        return (torch.empty((nq, kk), dtype=torch.float32, device=q.device),
+                torch.empty((nq, kk), dtype=torch.int64, device=q.device))
     if not q.is_cuda:
-        return sim_topk_ref(q, c, k, id_base, row_scale=row_scale)
+        return sim_topk_ref(q, c, k, id_base, row_scale=row_scale, mask=mask)
     nat = native()
+    if mask is not None:
+        n_live = mask.live.numel()
+        P = nat.sim_topk_splits_live(n_live, splits if splits is not None else auto_splits(N, nq, q.device))
+        ws = torch.empty((nq, P, k, 2), dtype=torch.float32, device=q.device)
+        scores = torch.empty((nq, kk), dtype=torch.float32, device=q.device)
+        ids = torch.empty((nq, kk), dtype=torch.int64, device=q.device)
+        stream = launch_stream(q)
+        if half:
+            nat.sim_topk_partial_masked_f16(ptr(q), ptr(c), ptr(row_scale) if row_scale is not None else 0,
+                                            ptr(mask.words), ptr(mask.live), ptr(ws), nq, N, D, k, P, n_live, stream)
+        else:
+            nat.sim_topk_partial_masked(ptr(q), ptr(c), ptr(mask.words), ptr(mask.live), ptr(ws), nq, N, D, k, P,
+                                        n_live, stream)
+        nat.sim_topk_merge(ptr(ws), ptr(scores), ptr(ids), nq, P, k, kk, int(id_base), stream)
+        return scores, ids
     P = nat.sim_topk_splits(N, splits if splits is not None else auto_splits(N, nq, q.device))
     ws = torch.empty((nq, P, k, 2), dtype=torch.float32, device=q.device)
     scores = torch.empty((nq, kk), dtype=torch.float32, device=q.device)

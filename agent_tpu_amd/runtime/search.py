@@ -34,6 +34,10 @@ F16_ERRORS: Dict[str, str] = {
     "corpus_f16_range": "corpus values exceed the float16 range",
     "corpus_too_large_f16": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float16",
 }
+#: that of a label file (``ops/map_search.py``: ``FILTER_ERRORS``)
+LABEL_ERRORS: Dict[str, str] = {
+    "labels_file": "corpus_labels_uri must be a local 1-D int32 or int64 .npy file with one label per corpus row",
+}
 DTYPES = ("float32", "float16")
 CHUNK_BYTES = 64 * 2 ** 20  # fp32 bytes of the row chunks that a float16 load checks and norms
 
@@ -48,6 +52,8 @@ class Corpus(NamedTuple):
 
 _lock = threading.Lock()
 _cache: "OrderedDict[Tuple, Tuple[torch.Tensor, Optional[torch.Tensor]]]" = OrderedDict()
+_label_cache: "OrderedDict[Tuple, torch.Tensor]" = OrderedDict()  # int64 label slices (load_labels)
+_label_stats = {"hits": 0, "loads": 0}
 
 
 def lru_capacity() -> int:
@@ -155,31 +161,78 @@ def load_corpus(uri: Any, start: int = 0, count: int = -1, normalize: bool = Tru
     return Corpus(vec, start, total, False, scale)
 
 
+def load_labels(uri: Any, start: int = 0, count: int = -1, device: torch.device = torch.device("cpu"),
+                total: Optional[int] = None) -> torch.Tensor:
+    """Labels ``[start, start + count)`` (``count < 0``: to the end) of a 1-D ``int32`` or ``int64``
+    ``.npy`` on ``device`` as int64; ``total``: the rows the file must have (one label per corpus
+    row). The slices stay in an LRU of their own, with the vector LRU's capacity and key form."""
+    import numpy as np
+
+    try:
+        path = os.path.realpath(local_path(uri))
+        st = os.stat(path)
+        arr = np.load(path, mmap_mode="r", allow_pickle=False)
+    except (OSError, ValueError, EOFError):
+        raise ValueError(LABEL_ERRORS["labels_file"]) from None
+    if not isinstance(arr, np.ndarray) or arr.ndim != 1 or arr.dtype.str not in ("<i4", "<i8") \
+            or (total is not None and arr.shape[0] != total):
+        raise ValueError(LABEL_ERRORS["labels_file"])
+    rows = int(arr.shape[0])
+    start = max(0, min(int(start), rows))
+    count = rows - start if count < 0 else max(0, min(int(count), rows - start))
+    key = (path, st.st_mtime_ns, st.st_size, start, count, str(device))
+    with _lock:
+        hit = _label_cache.get(key)
+        if hit is not None:
+            _label_cache.move_to_end(key)
+            _label_stats["hits"] += 1
+            return hit
+    lab = torch.from_numpy(np.array(arr[start:start + count], dtype=np.int64, order="C")).to(device).contiguous()
+    with _lock:
+        _label_stats["loads"] += 1
+        _label_cache[key] = lab
+        _label_cache.move_to_end(key)
+        while len(_label_cache) > lru_capacity():
+            _label_cache.popitem(last=False)
+    return lab
+
+
 def clear_cache() -> None:
     with _lock:
         _cache.clear()
+        _label_cache.clear()
 
 
 def cache_info() -> Dict[str, Any]:
+    """``entries``, ``capacity`` and ``resident_bytes`` speak of the vectors; the ``label_*`` keys of the
+    label LRU."""
     with _lock:
         return {"entries": [k[0] for k in _cache], "capacity": lru_capacity(),
                 "resident_bytes": sum(t.numel() * t.element_size() for v in _cache.values() for t in v
-                                      if t is not None)}
+                                      if t is not None),
+                "label_entries": [k[0] for k in _label_cache],
+                "label_bytes": sum(t.numel() * t.element_size() for t in _label_cache.values()),
+                "label_hits": _label_stats["hits"], "label_loads": _label_stats["loads"]}
 
 
 def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0,
-           row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+           row_scale: Optional[torch.Tensor] = None, mask=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(scores ``[nq, kk]`` fp32, ids ``[nq, kk]`` int64) of the fp32 ``qvecs [nq, dim]`` against
     ``corpus [rows, dim]`` (fp32, or fp16 with its optional ``row_scale [rows]``) on the corpus's
     device, ordered by (score desc, id asc). An empty slice
     (a DP rank beyond the corpus) gives ``kk = 0``. A shape the kernel does not take is an error,
-    never a detour through PyTorch."""
+    never a detour through PyTorch. ``mask`` (an ``ops.RowMask`` of the slice, on its device): only
+    its rows, ``kk = min(k, mask.count)``."""
     from .. import ops
 
     q = qvecs.to(device=corpus.device, dtype=torch.float32).contiguous()
     if corpus.shape[0] == 0:
         return (torch.empty((q.shape[0], 0), dtype=torch.float32, device=corpus.device),
                 torch.empty((q.shape[0], 0), dtype=torch.int64, device=corpus.device))
+    if mask is not None:  # its own calls, so that the unfiltered ones stay as they were
+        if not corpus.is_cuda:
+            return ops.sim_topk_ref(q, corpus, k, id_base, row_scale=row_scale, mask=mask)
+        return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale, mask=mask)
     if not corpus.is_cuda:
         return ops.sim_topk_ref(q, corpus, k, id_base, row_scale=row_scale)
     return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale)

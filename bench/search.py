@@ -14,6 +14,10 @@ byte), and TF/s (``2 * queries * N * D / t``). ``--splits`` overrides the automa
 ``ops.sim_topk(q, c16, k)`` over ``c16 = normalize(randn).half()`` (twice the buffers, so that the
 rotation covers the same bytes), B is ``ops.sim_topk(q, c16.float(), k)``. The corpus rate is then
 that of the bytes actually read (2 or 4 per element).
+
+``--filter-density d [d ...]`` with ``--filter-pattern {blocks,random}`` measures the row filter
+instead (:func:`filter_bench`): the unfiltered search, the masked one, torch's masked top-k and the
+gather routes, alternating; one JSON line per (N, queries, density, variant, round).
 """
 from __future__ import annotations
 
@@ -28,6 +32,74 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
+def filter_bench(a, ops, dev) -> int:
+    """``--filter-density``: what a row filter costs and saves, per (N, queries, density) point of
+    ``--filter-pattern``. Five arms alternate for ``--rounds`` rounds on the same tensors:
+    ``unfiltered`` (``sim_topk`` without a mask: the yardstick), ``masked`` (``sim_topk`` with the
+    mask), ``torch_masked_topk`` (``torch.topk((q @ c.T).masked_fill(~m, -inf), k)``; fp32 corpus
+    only), ``gather_then_sim_topk`` (``c[rows]`` gathered inside the timed call) and
+    ``sim_topk_on_gathered`` (the gather done beforehand). ``blocks`` allows one contiguous run of
+    rows (it starts at row N // 3 + 5, inside a word); ``random`` allows every row independently."""
+    D, k = a.dim, a.top_k
+    gen = torch.Generator(device=dev).manual_seed(0)
+    half = a.corpus_dtype == "float16"
+    size = 2 if half else 4
+    for N in a.rows:
+        nbuf = a.buffers if N * D * size < 512 * 2 ** 20 else 1
+        cs = [torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=gen), dim=1) for _ in range(nbuf)]
+        if half:
+            cs = [c.half() for c in cs]
+        for density in a.filter_density:
+            if a.filter_pattern == "blocks":
+                m = max(1, min(N, round(density * N)))
+                lo = min(N // 3 + 5, N - m)
+                n = torch.arange(N, device=dev)
+                bits = (n >= lo) & (n < lo + m)
+            else:
+                bits = torch.rand(N, device=dev, generator=gen) < density
+                bits[0] = True  # never empty
+            mask = ops.row_mask_from_bits(bits)
+            rows = bits.nonzero().flatten()
+            gathered = [c[rows].contiguous() for c in cs]
+            for nq in a.queries:
+                q = torch.nn.functional.normalize(torch.randn(nq, D, device=dev, generator=gen), dim=1)
+                arms = [("unfiltered", lambda i: ops.sim_topk(q, cs[i], k, splits=a.splits or None)),
+                        ("masked", lambda i: ops.sim_topk(q, cs[i], k, splits=a.splits or None, mask=mask))]
+                if not half:
+                    arms.append(("torch_masked_topk",
+                                 lambda i: torch.topk((q @ cs[i].T).masked_fill(~bits, float("-inf")), min(k, mask.count))))
+                arms += [("gather_then_sim_topk", lambda i: ops.sim_topk(q, cs[i][rows].contiguous(), k)),
+                         ("sim_topk_on_gathered", lambda i: ops.sim_topk(q, gathered[i], k))]
+
+                def timed(fn):
+                    for i in range(max(nbuf, 2)):
+                        fn(i % nbuf)
+                    torch.cuda.synchronize(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for it in range(a.iters):
+                        fn(it % nbuf)
+                    e1.record()
+                    torch.cuda.synchronize(dev)
+                    return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
+
+                ms, mi = arms[1][1](0)
+                gs, gi = arms[-1][1](0)
+                same = bool(torch.equal(ms, gs) and torch.equal(mi, rows[gi]))  # bit for bit, by construction
+                for r in range(a.rounds):
+                    for variant, fn in arms:
+                        us = timed(fn)
+                        print(json.dumps({"bench": "search_filter", "variant": variant, "pattern": a.filter_pattern,
+                                          "density": density, "N": N, "filter_rows": mask.count,
+                                          "live_words": int(mask.live.numel()), "words": int(mask.words.numel()),
+                                          "queries": nq, "dim": D, "top_k": k, "corpus_dtype": a.corpus_dtype,
+                                          "round": r, "us_per_call": round(us, 2),
+                                          "masked_equals_gathered": same}), flush=True)
+            del gathered
+        del cs
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
@@ -39,6 +111,9 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--corpus-dtype", choices=("float32", "float16"), default="float32")
+    ap.add_argument("--filter-density", type=float, nargs="+", default=None,
+                    help="run the row-filter comparison at these fractions of allowed rows instead")
+    ap.add_argument("--filter-pattern", choices=("blocks", "random"), default="blocks")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -46,6 +121,8 @@ def main() -> int:
     from agent_tpu_amd import ops
 
     dev = torch.device("cuda", 0)
+    if a.filter_density:
+        return filter_bench(a, ops, dev)
     D, k = a.dim, a.top_k
     gen = torch.Generator(device=dev).manual_seed(0)
     half = a.corpus_dtype == "float16"

@@ -4,7 +4,9 @@
 vectors given as numbers) are scored against a corpus (an ``.npy`` of ``map_embed``
 ``output: "npy"``, kept resident on the device, or texts embedded on the fly) by
 ``agent_tpu_amd/ops/search.py``: an exact fp32 similarity GEMM whose score matrix is never written,
-with the top-k taken in its epilogue (see map_search.CONTRACT.md).
+with the top-k taken in its epilogue (see map_search.CONTRACT.md). ``filter`` restricts the search to
+an allow-list or deny-list of row ids, or to the rows whose label (``corpus_labels_uri``) is in a set
+or a range: the rows become a bit mask on the device and the kernel applies it in its epilogue.
 
 Under ``torchrun`` every rank embeds the queries, searches its slice of the corpus, and rank 0
 merges the per-rank lists in the same total order (score descending, id ascending). Errors are
@@ -47,6 +49,18 @@ F16_ERRORS: Dict[str, str] = {
     "corpus_too_large_f16": "corpus slice exceeds SEARCH_INDEX_MAX_GB of float16",
 }
 CORPUS_DTYPES = ("float32", "float16")
+#: those of ``filter`` and ``corpus_labels_uri`` (also in the contract); ``{key}`` is ``ids`` or ``exclude_ids``
+FILTER_ERRORS: Dict[str, str] = {
+    "filter": "payload.filter must be an object with exactly one of 'ids', 'exclude_ids', 'labels', 'label_range'",
+    "filter_ids": "payload.filter.{key} must be a list of at most 1048576 integers in [0, corpus rows)",
+    "filter_labels": "payload.filter.labels must be a list of 1 to 256 integers",
+    "filter_label_range": "payload.filter.label_range must be [lo, hi] with integers lo <= hi",
+    "filter_labels_uri": "payload.filter on labels needs payload.corpus_labels_uri (with corpus_uri)",
+    "labels_file": "corpus_labels_uri must be a local 1-D int32 or int64 .npy file with one label per corpus row",
+}
+FILTER_KEYS = ("ids", "exclude_ids", "labels", "label_range")
+MAX_FILTER_IDS = 1048576
+MAX_FILTER_LABELS = 256
 
 
 class Options(NamedTuple):
@@ -55,10 +69,43 @@ class Options(NamedTuple):
     pooling: str
     min_score: Optional[float]
     corpus_dtype: str = "float32"  # residency of a corpus_uri corpus on the device
+    filter: Optional[tuple] = None  # canonical: (key, sorted unique values or the (lo, hi) pair)
+    labels_uri: Optional[str] = None  # corpus_labels_uri, kept only when a label filter uses it
 
 
 def _number(x: Any) -> bool:
     return isinstance(x, (int, float)) and not isinstance(x, bool) and math.isfinite(x)
+
+
+def _int64(x: Any) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63
+
+
+def parse_filter(payload: Dict[str, Any]):
+    """``payload.filter`` in canonical form, ``(key, values)``, and the label file it needs (or None):
+    everything about it that can be refused without the corpus."""
+    f = payload["filter"]
+    if not isinstance(f, dict) or len(f) != 1 or next(iter(f)) not in FILTER_KEYS:
+        raise ValueError(FILTER_ERRORS["filter"])
+    (key, v), = f.items()
+    if key in ("ids", "exclude_ids"):
+        if not isinstance(v, list) or len(v) > MAX_FILTER_IDS or not all(_int64(x) and x >= 0 for x in v):
+            raise ValueError(FILTER_ERRORS["filter_ids"].format(key=key))
+        return (key, tuple(sorted(set(v)))), None
+    if key == "labels":
+        if not isinstance(v, list) or not 1 <= len(v) <= MAX_FILTER_LABELS or not all(_int64(x) for x in v):
+            raise ValueError(FILTER_ERRORS["filter_labels"])
+        canon = (key, tuple(sorted(set(v))))
+    else:
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_int64(x) for x in v) or v[0] > v[1]:
+            raise ValueError(FILTER_ERRORS["filter_label_range"])
+        canon = (key, (v[0], v[1]))
+    if "corpus_uri" not in payload or "corpus_labels_uri" not in payload:
+        raise ValueError(FILTER_ERRORS["filter_labels_uri"])
+    uri = payload["corpus_labels_uri"]
+    if not isinstance(uri, str) or not uri or ("://" in uri and not uri.startswith("file://")):
+        raise ValueError(FILTER_ERRORS["labels_file"])
+    return canon, uri
 
 
 def options(payload: Dict[str, Any]) -> Options:
@@ -110,6 +157,9 @@ def check_payload(payload: Dict[str, Any]) -> Options:
             raise ValueError(ERRORS["corpus_texts"])
     else:
         raise ValueError(ERRORS["missing_corpus"])
+    if "filter" in payload:  # a job without one keeps its Options, its code path and its result keys
+        flt, labels_uri = parse_filter(payload)
+        opt = opt._replace(filter=flt, labels_uri=labels_uri)
     return opt
 
 
@@ -117,14 +167,38 @@ def _texts(rows: List[Any]) -> List[str]:
     return ["" if t is None else str(t) for t in rows]
 
 
+def slice_mask(flt, labels_uri, total: int, s_r: int, n_r: int, device):
+    """The ``ops.RowMask`` of rows ``[s_r, s_r + n_r)`` of a corpus of ``total`` rows for the canonical
+    filter ``flt`` (None for an empty slice): ids go in as they are, with the slice start as the
+    builder's base; labels are loaded for the slice only."""
+    from agent_tpu_amd import ops
+    from agent_tpu_amd.runtime import search as rs
+
+    key, vals = flt
+    if key in ("ids", "exclude_ids"):
+        if vals and vals[-1] >= total:  # sorted: the largest decides; the same on every rank
+            raise ValueError(FILTER_ERRORS["filter_ids"].format(key=key))
+        if n_r == 0:
+            return None
+        return ops.row_mask_from_ids(list(vals), n_r, base=s_r, exclude=key == "exclude_ids", device=device)
+    labels = rs.load_labels(labels_uri, s_r, n_r, device, total)  # every rank checks the file against total
+    if n_r == 0:
+        return None
+    if key == "labels":
+        return ops.row_mask_from_labels(labels, values=list(vals))
+    return ops.row_mask_from_labels(labels, lo=vals[0], hi=vals[1])
+
+
 def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, pooling: str,
-                   rank: int, ws: int, corpus_dtype: str = "float32"):
+                   rank: int, ws: int, corpus_dtype: str = "float32", flt=None, labels_uri=None):
     """Every rank: this rank's slice of the corpus (resident as ``corpus_dtype`` in the ``corpus_uri``
     form) searched for all ``qvecs [nq, dim]`` (host or device fp32, already normalised for
     cosine), the per-rank lists padded to ``top_k``,
     all-gathered and merged. -> (scores ``[nq, kk]``, ids ``[nq, kk]`` on the host, corpus rows,
-    index_cached or None) on rank 0, None elsewhere. Local errors are exchanged before the
-    collective, so a bad corpus fails every rank together with the single-process message."""
+    index_cached or None, filter_rows or None) on rank 0, None elsewhere. Local errors are exchanged
+    before the collective, so a bad corpus fails every rank together with the single-process message.
+    With a filter ``flt`` (canonical form) every rank masks its own slice; the ranks' counts of allowed
+    rows travel with the error exchange, and their sum is ``filter_rows``."""
     import torch
 
     from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
@@ -132,7 +206,7 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
     from agent_tpu_amd.runtime import search as rs
 
     cosine = metric == "cosine"
-    exc, s, i, total, cached, scale = None, None, None, 0, None, None
+    exc, s, i, total, cached, scale, allowed = None, None, None, 0, None, None, 0
     nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
     try:
         if "corpus_uri" in payload:
@@ -150,14 +224,24 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
             s_r, n_r = split_range(0, total, ws, rank)
             vec = h.engine.embed_texts(texts[s_r:s_r + n_r], pooling, cosine).emb.to(device)
         maybe_inject_fault("search")
-        s, i = rs.search(qvecs, vec, top_k, id_base=s_r, row_scale=scale)
+        if flt is None:
+            s, i = rs.search(qvecs, vec, top_k, id_base=s_r, row_scale=scale)
+        else:
+            mask = slice_mask(flt, labels_uri, total, s_r, n_r, vec.device)
+            allowed = mask.count if mask is not None else 0
+            s, i = rs.search(qvecs, vec, top_k, id_base=s_r, row_scale=scale, mask=mask)
         if s.shape[1] < top_k:  # a slice shorter than top_k: pad, so every rank gathers [nq, top_k]
             pad = top_k - s.shape[1]
             s = torch.cat([s, torch.full((nq, pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
             i = torch.cat([i, torch.full((nq, pad), PAD_ID, dtype=i.dtype, device=i.device)], 1)
     except Exception as e:
         exc = e
-    counts = exchange_errors(exc, nq if s is not None else 0)
+    filter_rows = None
+    if flt is None:
+        counts = exchange_errors(exc, nq if s is not None else 0)
+    else:  # (rows, allowed rows of the slice) in the same object exchange
+        extras = exchange_errors(exc, (nq if s is not None else 0, allowed))
+        counts, filter_rows = [e[0] for e in extras], sum(e[1] for e in extras)
     s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
     if rank != 0:
         return None
@@ -166,8 +250,8 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
         s = s.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
         i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
         s, i = rs.merge_topk(s, i, top_k)
-    kk = min(top_k, total)
-    return s[:, :kk], i[:, :kk], total, cached
+    kk = min(top_k, total if filter_rows is None else filter_rows)
+    return s[:, :kk], i[:, :kk], total, cached, filter_rows
 
 
 def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str]], metric: str, pooling: str):
@@ -185,11 +269,12 @@ def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str
 
 
 def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim: int, cached: Optional[bool],
-           ws: int) -> Dict[str, Any]:
+           ws: int, filter_rows: Optional[int] = None) -> Dict[str, Any]:
     """One job's result from its rows of the merged lists (rank 0): the first ``top_k`` entries (with
-    a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host."""
+    a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host.
+    ``filter_rows``: the corpus rows that passed the job's filter (None: no filter)."""
     opt = options(payload)
-    kk = min(top_k, total)
+    kk = min(top_k, total if filter_rows is None else filter_rows)
     ids_l, sc_l = ids[:, :kk].tolist(), scores[:, :kk].tolist()
     if opt.min_score is not None:
         keep = [[j for j, v in enumerate(row) if v >= opt.min_score] for row in sc_l]
@@ -208,6 +293,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         out["index_cached"] = bool(cached)
     if "corpus_uri" in payload and opt.corpus_dtype != "float32":  # default-path results keep their keys
         out["corpus_dtype"] = opt.corpus_dtype
+    if filter_rows is not None:
+        out["filter_rows"] = int(filter_rows)
     out.update(ids=ids_l, scores=sc_l)
     return out
 
@@ -238,17 +325,18 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         qv = torch.zeros((0, dim), dtype=torch.float32) if h is not None else None
         if qv is None:
             raise ValueError(ERRORS["query_vectors"])
-    got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype)
+    got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
+                         opt.filter, opt.labels_uri)
     if got is None:
         return None
-    s, i, total, cached = got
-    return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws)
+    s, i, total, cached, filter_rows = got
+    return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, filter_rows)
 
 
 def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional[List[Any]]:
     """The ``queries`` + ``corpus_uri`` jobs of one lease that share (model, pooling, metric, corpus,
-    corpus_dtype) as one engine call (every rank calls it): one embed of the concatenated queries,
-    one search at the
+    corpus_dtype, canonical filter and its label file) as one engine call (every rank calls it): one
+    embed of the concatenated queries, one search at the
     group's largest ``top_k``; each job takes the first ``top_k`` entries of its own rows."""
     out: List[Any] = [None] * len(payloads)
     jobs = []
@@ -272,17 +360,18 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 import torch
 
                 qv = torch.cat([h.engine.embed_texts(ts, key.pooling, key.metric == "cosine").emb for _, _, ts in jobs])
-            got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype)
+            got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
+                                 key.filter, key.labels_uri)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
                 out[n] = ("err", exc)
             return out if rank == 0 else None
         if got is not None:
-            s, i, total, cached = got
+            s, i, total, cached, filter_rows = got
             pos = 0
             for n, opt, ts in jobs:
                 out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
-                                       int(qv.shape[1]), cached, ws))
+                                       int(qv.shape[1]), cached, ws, filter_rows))
                 pos += len(ts)
     return out if rank == 0 else None
 
@@ -290,15 +379,16 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 @register_batch_op("map_search")
 def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``queries`` + ``corpus_uri`` jobs that share (model_path, pooling, metric,
-    corpus_uri, corpus_dtype) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs
-    and malformed
-    payloads take the single-job path."""
+    corpus_uri, corpus_dtype, and with a ``filter`` its canonical form and label file) go to the
+    device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
+    single-job path."""
 
     def key(p):
         if "queries" not in p or "corpus_uri" not in p:
             raise KeyError("queries")  # not batchable
         opt = check_payload(p)
-        return p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype
+        group = p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype
+        return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
     return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
 
