@@ -304,6 +304,33 @@ PYBIND11_MODULE(_atpu, m) {
       "merge of the per-split lists of sim_topk_partial in (value desc, row asc) order",
       py::arg("ws"), py::arg("scores"), py::arg("ids"), py::arg("nq"), py::arg("P"), py::arg("k"), py::arg("kk"),
       py::arg("id_base"), py::arg("stream"));
+  m.def("sim_topk_ivf_items", &sim_topk_ivf_items,
+        "the work-item bound that sim_topk_ivf_partial is launched with: min(nq * nprobe, K) + nq * nprobe / 16",
+        py::arg("nq"), py::arg("nprobe"), py::arg("K"));
+  m.def(
+      "sim_topk_ivf_plan",
+      [](uintptr_t probes, int nq, int nprobe, int K, int items, uintptr_t item_cluster, uintptr_t item_query,
+         uintptr_t item_slot, uintptr_t stream) {
+        sim_topk_ivf_plan(P<const int64_t>(probes), nq, nprobe, K, items, P<int32_t>(item_cluster),
+                          P<int32_t>(item_query), P<int32_t>(item_slot), S(stream));
+      },
+      "the work items of probes [nq, nprobe] int64: item_cluster [items], item_query and item_slot [items, 16]",
+      py::arg("probes"), py::arg("nq"), py::arg("nprobe"), py::arg("K"), py::arg("items"), py::arg("item_cluster"),
+      py::arg("item_query"), py::arg("item_slot"), py::arg("stream"));
+  m.def(
+      "sim_topk_ivf_partial",
+      [](uintptr_t q, uintptr_t vectors, uintptr_t row_ids, uintptr_t offsets, uintptr_t item_cluster,
+         uintptr_t item_query, uintptr_t item_slot, uintptr_t ws, int nq, int N, int D, int k, int K, int nprobe,
+         int splits, int items, uintptr_t stream) {
+        sim_topk_ivf_partial(P<const float>(q), P<const float>(vectors), P<const int32_t>(row_ids),
+                             P<const int32_t>(offsets), P<const int32_t>(item_cluster), P<const int32_t>(item_query),
+                             P<const int32_t>(item_slot), P<float>(ws), nq, N, D, k, K, nprobe, splits, items, S(stream));
+      },
+      "sim_topk over the cluster-sorted vectors, each query against the clusters of its probe slots: the sorted "
+      "top-k (value, original row) of every (query, slot, split) to ws [nq, nprobe * S, k, 2]",
+      py::arg("q"), py::arg("vectors"), py::arg("row_ids"), py::arg("offsets"), py::arg("item_cluster"),
+      py::arg("item_query"), py::arg("item_slot"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"),
+      py::arg("k"), py::arg("K"), py::arg("nprobe"), py::arg("S"), py::arg("items"), py::arg("stream"));
   m.def("kmeans_shape_ok", &kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
   m.def(
       "kmeans_assign",

@@ -179,6 +179,25 @@ void row_mask_from_ids(const int64_t* ids, int64_t m, int64_t base, int N, int e
                        int64_t* count, hipStream_t stream);
 void row_mask_from_labels(const int64_t* labels, int N, const int64_t* values, int m, int64_t lo, int64_t hi,
                           int32_t* words, int64_t* count, hipStream_t stream);
+// IVF form (sim_topk_ivf.hip): the corpus sorted by cluster, vectors [N, D] fp32 with row_ids [N] int32 (the
+// original row of a sorted row) and offsets [K + 1] int32; every query searches the clusters of its own
+// nprobe probe slots. The plan groups the nq * nprobe (query, slot) pairs by cluster into `items` work items
+// of at most kIvfItemQueries queries of one cluster: item_cluster [items] (negative: a surplus item),
+// item_query / item_slot [items, 16] (negative slot: padding, its query a valid one). One workgroup per
+// (item, split of S) leaves the sorted top-k (value, ORIGINAL row) of (query, slot, split) in
+// ws [nq, nprobe * S, k, 2] fp32, every slot written, for sim_topk_merge with P = nprobe * S <= kSimMaxSplits.
+// A score has sim_topk's bits for the same (q, row). K in [1, 4096], nprobe in [1, min(32, K)];
+// items <= sim_topk_ivf_items(nq, nprobe, K) = min(nq * nprobe, K) + nq * nprobe / 16, the bound to launch.
+// Nothing outside q, vectors[0:N], row_ids[0:N], offsets[0:K + 1] and the plan arrays is read.
+constexpr int kIvfItemQueries = 16;
+int64_t sim_topk_ivf_items(int64_t nq, int nprobe, int K);
+// The plan of probes [nq, nprobe] int64 (cluster ids in [0, K); others are skipped) in one launch: the three plan
+// arrays written whole, items == sim_topk_ivf_items(nq, nprobe, K). Every pair lands in exactly one item.
+void sim_topk_ivf_plan(const int64_t* probes, int nq, int nprobe, int K, int items, int32_t* item_cluster,
+                       int32_t* item_query, int32_t* item_slot, hipStream_t stream);
+void sim_topk_ivf_partial(const float* q, const float* vectors, const int32_t* row_ids, const int32_t* offsets,
+                          const int32_t* item_cluster, const int32_t* item_query, const int32_t* item_slot, float* ws,
+                          int nq, int N, int D, int k, int K, int nprobe, int S, int items, hipStream_t stream);
 
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)

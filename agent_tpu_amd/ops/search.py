@@ -30,6 +30,11 @@ The filter sits in the kernel's epilogue, and a score keeps the bits it has with
 ``sim_topk(q, c, k, mask=m)`` equals ``sim_topk(q, c[rows], k)`` over the allowed rows with the ids
 mapped back, bit for bit, at ``kk = min(k, m.count)`` columns. :func:`row_mask_from_ids` and
 :func:`row_mask_from_labels` build masks on the device (``*_ref``: their PyTorch twins).
+
+:func:`sim_topk_ivf` (``csrc/kernels/sim_topk_ivf.hip``) is the approximate form: the corpus sorted by
+k-means cluster, and every query scored against the rows of the ``nprobe`` clusters nearest to it only, a
+different row set per query. The scores stay exact fp32 dot products with ``sim_topk``'s bits and the ids are
+the original rows, so probing every cluster is the exact search bit for bit.
 """
 from __future__ import annotations
 
@@ -269,3 +274,157 @@ def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits:
         nat.sim_topk_partial(ptr(q), ptr(c), ptr(ws), nq, N, D, k, P, stream)
     nat.sim_topk_merge(ptr(ws), ptr(scores), ptr(ids), nq, P, k, kk, int(id_base), stream)
     return scores, ids
+
+
+# ------------------------------------------------------------------------------------------------ IVF
+PAD_ID = 2 ** 62  # id of the (-inf) padding past a query's count
+IVF_QT = 16  # kIvfItemQueries: queries of one cluster per work item
+IVF_MAX_CLUSTERS = 4096  # kKmeansMaxK
+_NO_ROW = 0x7fffffff  # kNoRow: the id of an empty list entry
+
+
+def _check_ivf(q, vectors, row_ids, offsets, centroids, k, nprobe, id_base, splits):
+    check(q.dim() == 2 and vectors.dim() == 2 and centroids.dim() == 2 and q.shape[1] == vectors.shape[1]
+          and q.shape[1] == centroids.shape[1], "sim_topk_ivf: q [nq, D], vectors [n, D] and centroids [K, D]")
+    check(q.dtype == torch.float32 and vectors.dtype == torch.float32 and centroids.dtype == torch.float32,
+          "sim_topk_ivf: q, vectors and centroids must be fp32")
+    n, K = vectors.shape[0], centroids.shape[0]
+    check(0 <= n <= MAX_ROWS, "sim_topk_ivf: n must be in [0, 2^31 - 256]")
+    check(isinstance(k, int) and not isinstance(k, bool) and sim_topk_ok(q.shape[1], k),
+          f"sim_topk_ivf: unsupported shape D={q.shape[1]} k={k}")
+    check(1 <= K <= IVF_MAX_CLUSTERS, "sim_topk_ivf: K must be in [1, 4096]")
+    check(isinstance(nprobe, int) and not isinstance(nprobe, bool) and 1 <= nprobe <= min(MAX_K, K),
+          "sim_topk_ivf: nprobe must be in [1, min(32, K)]")
+    check(row_ids.dtype == torch.int32 and row_ids.shape == (n,) and offsets.dtype == torch.int32
+          and offsets.shape == (K + 1,), "sim_topk_ivf: row_ids must be int32 [n] and offsets int32 [K + 1]")
+    check(all(t.is_contiguous() for t in (q, vectors, row_ids, offsets, centroids)), "sim_topk_ivf: contiguous tensors")
+    check(isinstance(id_base, int) and 0 <= id_base < 2 ** 61, "sim_topk_ivf: id_base must be in [0, 2^61)")
+    check(splits is None or (isinstance(splits, int) and 1 <= splits * nprobe <= MAX_SPLITS),
+          f"sim_topk_ivf: nprobe * splits must be in [1, {MAX_SPLITS}]")
+    same_device(q, vectors, row_ids, offsets, centroids)
+
+
+def _ivf_pad(scores: torch.Tensor, ids: torch.Tensor, empty: torch.Tensor):
+    """(scores, ids, counts) with ``(-inf, PAD_ID)`` in the ``empty`` columns (they sort last: a suffix)."""
+    scores = torch.where(empty, torch.full_like(scores, float("-inf")), scores)
+    ids = torch.where(empty, torch.full_like(ids, PAD_ID), ids)
+    return scores, ids, (~empty).sum(1)
+
+
+def ivf_labels(row_ids: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """int64 ``[n]``: the cluster of every ORIGINAL row of an index (the inverse of the sort)."""
+    n, K = row_ids.numel(), offsets.numel() - 1
+    sizes = (offsets[1:] - offsets[:-1]).to(torch.int64)
+    by_pos = torch.repeat_interleave(torch.arange(K, device=offsets.device), sizes, output_size=n)
+    labels = torch.empty((n,), dtype=torch.int64, device=row_ids.device)
+    labels[row_ids.to(torch.int64)] = by_pos
+    return labels
+
+
+def sim_topk_ivf_ref(q: torch.Tensor, vectors: torch.Tensor, row_ids: torch.Tensor, offsets: torch.Tensor,
+                     centroids: torch.Tensor, k: int, nprobe: int, id_base: int = 0
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """PyTorch twin of :func:`sim_topk_ivf` and the CPU path: per query, ``sim_topk_ref`` with the mask
+    "the row's cluster is in the query's probe list" over the rows put back in their original order."""
+    _check_ivf(q, vectors, row_ids, offsets, centroids, k, nprobe, id_base, None)
+    nq, n = q.shape[0], vectors.shape[0]
+    if nq == 0 or n == 0:
+        return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=q.device),
+                torch.full((nq, k), PAD_ID, dtype=torch.int64, device=q.device),
+                torch.zeros((nq,), dtype=torch.int64, device=q.device))
+    probes = sim_topk_ref(q, centroids, nprobe)[1]  # [nq, nprobe]
+    x = torch.empty_like(vectors)
+    x[row_ids.to(torch.int64)] = vectors
+    labels = ivf_labels(row_ids, offsets)
+    allowed = torch.zeros((nq, n), dtype=torch.bool, device=q.device)
+    for j in range(nprobe):
+        allowed |= labels[None, :] == probes[:, j:j + 1]
+    s = (q @ x.T).masked_fill(~allowed, float("-inf"))  # by select: a NaN outside the probed clusters cannot leak
+    order = torch.sort(s + 0.0, dim=1, descending=True, stable=True).indices[:, :k]
+    scores, ids = torch.gather(s, 1, order), order.to(torch.int64) + int(id_base)
+    empty = ~torch.gather(allowed, 1, order)
+    if scores.shape[1] < k:  # fewer rows than k
+        pad = k - scores.shape[1]
+        scores = torch.cat([scores, scores.new_full((nq, pad), float("-inf"))], 1)
+        ids = torch.cat([ids, ids.new_full((nq, pad), PAD_ID)], 1)
+        empty = torch.cat([empty, empty.new_ones((nq, pad))], 1)
+    return _ivf_pad(scores, ids, empty)
+
+
+def ivf_plan(probes: torch.Tensor, K: int, items: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The work items of a probe table ``[nq, nprobe]`` (cluster ids), built on its device with no copy back:
+    (item_cluster ``[items]``, item_query ``[items, 16]``, item_slot ``[items, 16]``), all int32. The
+    ``nq * nprobe`` (query, slot) pairs are sorted by cluster (stable: ascending query inside one) and cut into
+    items of at most 16 queries of one cluster; every pair lands in exactly one item. ``items`` is the launch
+    bound ``min(nq * nprobe, K) + nq * nprobe // 16``: a cluster with ``m`` pairs takes ``ceil(m / 16)``, at
+    most one more than ``m // 16``. Surplus items keep cluster ``-1``, padding slots ``-1`` and a valid query.
+    On the GPU one small kernel does it in one launch (``sim_topk_ivf_plan``; a pair's slot inside its cluster is
+    then whatever the atomics gave, which the search does not depend on); this function's own PyTorch calls are
+    its twin and the CPU path."""
+    nq, nprobe = probes.shape
+    dev = probes.device
+    check(probes.dim() == 2 and probes.dtype == torch.int64 and probes.is_contiguous() and nq >= 1 and nprobe >= 1,
+          "ivf_plan: probes must be a contiguous int64 [nq, nprobe]")
+    if probes.is_cuda:
+        item_cluster = torch.empty((items,), dtype=torch.int32, device=dev)
+        item_query = torch.empty((items, IVF_QT), dtype=torch.int32, device=dev)
+        item_slot = torch.empty((items, IVF_QT), dtype=torch.int32, device=dev)
+        native().sim_topk_ivf_plan(ptr(probes), nq, nprobe, K, items, ptr(item_cluster), ptr(item_query), ptr(item_slot),
+                                   launch_stream(probes))
+        return item_cluster, item_query, item_slot
+    cl, pair = torch.sort(probes.reshape(-1), stable=True)
+    per = torch.zeros((K,), dtype=torch.int64, device=dev).scatter_add_(0, cl, torch.ones_like(cl))
+    first = torch.cumsum(per, 0) - per  # the sorted position of a cluster's first pair
+    n_items = (per + (IVF_QT - 1)) // IVF_QT
+    item0 = torch.cumsum(n_items, 0) - n_items  # a cluster's first item
+    rank = torch.arange(cl.numel(), device=dev) - first[cl]
+    item, lane = item0[cl] + rank // IVF_QT, rank % IVF_QT
+    item_cluster = torch.full((items,), -1, dtype=torch.int32, device=dev)
+    item_query = torch.zeros((items, IVF_QT), dtype=torch.int32, device=dev)
+    item_slot = torch.full((items, IVF_QT), -1, dtype=torch.int32, device=dev)
+    item_cluster[item] = cl.to(torch.int32)
+    item_query[item, lane] = (pair // nprobe).to(torch.int32)
+    item_slot[item, lane] = (pair % nprobe).to(torch.int32)
+    item_query = torch.where(item_slot >= 0, item_query, item_query[:, :1])  # padding repeats the item's first query
+    return item_cluster, item_query.contiguous(), item_slot
+
+
+def ivf_splits(nq: int, nprobe: int, K: int, n: int, device: torch.device) -> int:
+    """Splits per work item: enough workgroups (three of the 16-query form fit a CU) for the item bound, no more
+    than a cluster of average size has 32-row steps, and ``nprobe * S <= 256`` lists per query for the merge."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    bound = min(nq * nprobe, K) + nq * nprobe // IVF_QT
+    steps = max(1, -(-n // (32 * K)))
+    return max(1, min(MAX_SPLITS // nprobe, -(-3 * cus // bound), steps))
+
+
+def sim_topk_ivf(q: torch.Tensor, vectors: torch.Tensor, row_ids: torch.Tensor, offsets: torch.Tensor,
+                 centroids: torch.Tensor, k: int, nprobe: int, id_base: int = 0, splits: Optional[int] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(scores ``[nq, k]`` fp32, ids ``[nq, k]`` int64, counts ``[nq]`` int64) of the fp32 ``q [nq, D]`` against
+    an IVF index (``csrc/kernels/sim_topk_ivf.hip``): ``vectors [n, D]`` fp32 sorted by cluster, ``row_ids [n]``
+    int32 (the original row of a sorted row, ascending inside a cluster), ``offsets [K + 1]`` int32 and the
+    ``centroids [K, D]``. Query ``i`` searches the ``nprobe`` clusters whose centroids score best against it
+    (``sim_topk(q, centroids, nprobe)``: fixed bits whatever the batch); ``ids = id_base + original row``, in the
+    (score desc, id asc) order of the exact search, and a score has ``sim_topk``'s bits. The columns past
+    ``counts[i]`` (fewer than ``k`` rows in the probed clusters) hold ``(-inf, PAD_ID)``. The result does not
+    depend on ``splits`` (tests and benches) or on the batch; with ``nprobe == K`` it is ``sim_topk``'s."""
+    _check_ivf(q, vectors, row_ids, offsets, centroids, k, nprobe, id_base, splits)
+    nq, D = q.shape
+    n, K = vectors.shape[0], centroids.shape[0]
+    if not q.is_cuda or nq == 0 or n == 0:
+        return sim_topk_ivf_ref(q, vectors, row_ids, offsets, centroids, k, nprobe, id_base)
+    nat = native()
+    probes = sim_topk(q, centroids, nprobe)[1]
+    items = int(nat.sim_topk_ivf_items(nq, nprobe, K))
+    item_cluster, item_query, item_slot = ivf_plan(probes, K, items)
+    S = splits if splits is not None else ivf_splits(nq, nprobe, K, n, q.device)
+    P = nprobe * S
+    ws = torch.empty((nq, P, k, 2), dtype=torch.float32, device=q.device)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    stream = launch_stream(q)
+    nat.sim_topk_ivf_partial(ptr(q), ptr(vectors), ptr(row_ids), ptr(offsets), ptr(item_cluster), ptr(item_query),
+                             ptr(item_slot), ptr(ws), nq, n, D, k, K, nprobe, S, items, stream)
+    nat.sim_topk_merge(ptr(ws), ptr(scores), ptr(ids), nq, P, k, k, int(id_base), stream)
+    return _ivf_pad(scores, ids, ids == int(id_base) + _NO_ROW)  # the merge's empty entries: (-inf, id_base + kNoRow)

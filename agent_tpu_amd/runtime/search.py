@@ -10,6 +10,9 @@ misses). :func:`search` is ``ops.sim_topk`` on the GPU and its PyTorch twin on a
 With ``dtype="float16"`` the resident rows are fp16 (a ``float16`` file as it is, a ``float32`` file
 rounded to nearest) at half the bytes, and cosine keeps the rows unnormalised beside an fp32
 ``row_scale = 1 / max(||row||_2, 1e-12)`` that ``sim_topk`` multiplies into the finished score.
+
+The IVF indexes of ``runtime/ivf.py`` are entries of the same LRU, under the corpus key extended by
+``("ivf", clusters, train_iterations)``.
 """
 from __future__ import annotations
 
@@ -209,7 +212,7 @@ def cache_info() -> Dict[str, Any]:
     with _lock:
         return {"entries": [k[0] for k in _cache], "capacity": lru_capacity(),
                 "resident_bytes": sum(t.numel() * t.element_size() for v in _cache.values() for t in v
-                                      if t is not None),
+                                      if isinstance(t, torch.Tensor)),  # an IVF entry (runtime/ivf.py) ends in two scalars
                 "label_entries": [k[0] for k in _label_cache],
                 "label_bytes": sum(t.numel() * t.element_size() for t in _label_cache.values()),
                 "label_hits": _label_stats["hits"], "label_loads": _label_stats["loads"]}

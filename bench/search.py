@@ -18,6 +18,10 @@ that of the bytes actually read (2 or 4 per element).
 ``--filter-density d [d ...]`` with ``--filter-pattern {blocks,random}`` measures the row filter
 instead (:func:`filter_bench`): the unfiltered search, the masked one, torch's masked top-k and the
 gather routes, alternating; one JSON line per (N, queries, density, variant, round).
+
+``--ivf-clusters K`` with ``--nprobe n [n ...]`` measures the IVF index instead (:func:`ivf_bench`): the
+exact search and ``ops.sim_topk_ivf`` on the same tensors, alternating, with recall against the exact result,
+the build time and the probe-and-plan time; one JSON line per (N, queries, nprobe, variant, round).
 """
 from __future__ import annotations
 
@@ -100,6 +104,86 @@ def filter_bench(a, ops, dev) -> int:
     return 0
 
 
+def ivf_bench(a, ops, dev) -> int:
+    """``--ivf-clusters K`` with ``--nprobe n [n ...]``: the IVF search against the exact one on the same
+    tensors. The corpus is a seeded mixture of ``K`` Gaussians (unit-norm centres, noise of
+    ``--ivf-noise`` per column, rows normalised): no real embeddings are at hand, so the recall figures say how the
+    index does on clustered synthetic data, not on a text corpus. The index is built by ``runtime.ivf.build``
+    (timed once, host clock around a synchronise). Per (N, queries, nprobe) two arms alternate for ``--rounds``
+    rounds: ``exact`` (``ops.sim_topk`` over the original-order rows) and ``ivf`` (``ops.sim_topk_ivf``, the
+    probe and the plan included); ``--query-sets`` query batches rotate in both arms, so that a call does not
+    find the clusters it probes in the Infinity Cache from the call before. ``plan_us`` is the probe plus the
+    plan alone, ``recall`` the mean share of the exact top-k that the IVF list holds."""
+    import time
+
+    from agent_tpu_amd.runtime import ivf
+    from agent_tpu_amd.runtime.search import normalize_rows
+
+    D, k, K = a.dim, a.top_k, a.ivf_clusters
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def mixture(n, centres):
+        pick = torch.randint(0, centres.shape[0], (n,), device=dev, generator=gen)
+        return normalize_rows(centres[pick] + a.ivf_noise * torch.randn(n, D, device=dev, generator=gen)).contiguous()
+
+    for N in a.rows:
+        centres = normalize_rows(torch.randn(K, D, device=dev, generator=gen))
+        x = mixture(N, centres)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        vec, rid, off, cent, iters, converged = ivf.build(x, K, a.ivf_train_iterations)
+        torch.cuda.synchronize(dev)
+        build_ms = (time.perf_counter() - t0) * 1e3
+        sizes = (off[1:] - off[:-1]).float()
+        for nq in a.queries:
+            qs = [mixture(nq, centres) for _ in range(a.query_sets)]
+            for nprobe in a.nprobe:
+                items = int(min(nq * nprobe, K) + nq * nprobe // 16)
+
+                def exact(i):
+                    return ops.sim_topk(qs[i], x, k, splits=a.splits or None)
+
+                def approx(i):
+                    return ops.sim_topk_ivf(qs[i], vec, rid, off, cent, k, nprobe)
+
+                def plan(i):
+                    return ops.ivf_plan(ops.sim_topk(qs[i], cent, nprobe)[1], K, items)
+
+                def timed(fn):
+                    for i in range(a.query_sets):
+                        fn(i)
+                    torch.cuda.synchronize(dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for it in range(a.iters):
+                        fn(it % a.query_sets)
+                    e1.record()
+                    torch.cuda.synchronize(dev)
+                    return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
+
+                hit = 0
+                for i in range(a.query_sets):
+                    ei, ai = exact(i)[1], approx(i)[1]
+                    hit += int((ai[:, :, None] == ei[:, None, :]).any(1).sum())
+                recall = hit / (a.query_sets * nq * k)
+                full = approx(0) if nprobe == K else None
+                for r in range(a.rounds):
+                    for variant, fn in (("exact", exact), ("ivf", approx), ("ivf_probe_and_plan", plan)):
+                        us = timed(fn)
+                        print(json.dumps({"bench": "search_ivf", "variant": variant, "N": N, "queries": nq, "dim": D,
+                                          "top_k": k, "clusters": K, "nprobe": nprobe, "round": r,
+                                          "us_per_call": round(us, 2), "recall": round(recall, 4),
+                                          "build_ms": round(build_ms, 1), "train_iterations": iters,
+                                          "converged": converged, "largest_cluster": int(sizes.max()),
+                                          "mean_cluster": round(float(sizes.mean()), 1), "noise": a.ivf_noise,
+                                          "query_sets": a.query_sets,
+                                          "splits": ops.search.ivf_splits(nq, nprobe, K, N, dev),
+                                          "exact_when_all_probed": None if full is None else bool(
+                                              torch.equal(full[1], exact(0)[1]))}), flush=True)
+        del x, vec
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
@@ -114,6 +198,11 @@ def main() -> int:
     ap.add_argument("--filter-density", type=float, nargs="+", default=None,
                     help="run the row-filter comparison at these fractions of allowed rows instead")
     ap.add_argument("--filter-pattern", choices=("blocks", "random"), default="blocks")
+    ap.add_argument("--ivf-clusters", type=int, default=0, help="run the IVF comparison with this many clusters instead")
+    ap.add_argument("--nprobe", type=int, nargs="+", default=[1, 8, 32])
+    ap.add_argument("--ivf-train-iterations", type=int, default=10)
+    ap.add_argument("--ivf-noise", type=float, default=0.05, help="per-column noise of the IVF mixture corpus")
+    ap.add_argument("--query-sets", type=int, default=16, help="query batches that the IVF comparison rotates through")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -123,6 +212,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     if a.filter_density:
         return filter_bench(a, ops, dev)
+    if a.ivf_clusters:
+        return ivf_bench(a, ops, dev)
     D, k = a.dim, a.top_k
     gen = torch.Generator(device=dev).manual_seed(0)
     half = a.corpus_dtype == "float16"

@@ -7,6 +7,9 @@ vectors given as numbers) are scored against a corpus (an ``.npy`` of ``map_embe
 with the top-k taken in its epilogue (see map_search.CONTRACT.md). ``filter`` restricts the search to
 an allow-list or deny-list of row ids, or to the rows whose label (``corpus_labels_uri``) is in a set
 or a range: the rows become a bit mask on the device and the kernel applies it in its epilogue.
+``index`` asks for an approximate search through an inverted-file (IVF) index: the resident corpus sorted by
+k-means cluster (``agent_tpu_amd/runtime/ivf.py``), every query scored against the rows of the ``nprobe``
+clusters nearest to it only (``ops.sim_topk_ivf``); the scores stay exact and the ids are the original rows.
 
 Under ``torchrun`` every rank embeds the queries, searches its slice of the corpus, and rank 0
 merges the per-rank lists in the same total order (score descending, id ascending). Errors are
@@ -61,6 +64,20 @@ FILTER_ERRORS: Dict[str, str] = {
 FILTER_KEYS = ("ids", "exclude_ids", "labels", "label_range")
 MAX_FILTER_IDS = 1048576
 MAX_FILTER_LABELS = 256
+#: those of ``index`` (also in the contract)
+IVF_ERRORS: Dict[str, str] = {
+    "index": ("payload.index must be {'type': 'ivf'} with optional integers 'clusters' in [1, min(4096, corpus rows)], "
+              "'nprobe' in [1, min(32, clusters)] and 'train_iterations' in [1, 100]"),
+    "index_corpus": "payload.index needs payload.corpus_uri (a resident corpus)",
+    "index_metric": "payload.index needs metric 'cosine'",
+    "index_f16": "payload.index needs a float32-resident corpus (corpus_dtype or SEARCH_INDEX_DTYPE is 'float16')",
+    "index_filter": "payload.index cannot be combined with payload.filter",
+    "index_too_large": "index build exceeds SEARCH_INDEX_MAX_GB (two float32 copies of the corpus slice)",
+}
+INDEX_KEYS = ("type", "clusters", "nprobe", "train_iterations")
+MAX_CLUSTERS = 4096
+MAX_NPROBE = 32  # sim_topk's MAX_K: the probe is a sim_topk call
+MAX_TRAIN_ITERATIONS = 100
 
 
 class Options(NamedTuple):
@@ -71,6 +88,7 @@ class Options(NamedTuple):
     corpus_dtype: str = "float32"  # residency of a corpus_uri corpus on the device
     filter: Optional[tuple] = None  # canonical: (key, sorted unique values or the (lo, hi) pair)
     labels_uri: Optional[str] = None  # corpus_labels_uri, kept only when a label filter uses it
+    index: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, train_iterations)
 
 
 def _number(x: Any) -> bool:
@@ -106,6 +124,54 @@ def parse_filter(payload: Dict[str, Any]):
     if not isinstance(uri, str) or not uri or ("://" in uri and not uri.startswith("file://")):
         raise ValueError(FILTER_ERRORS["labels_file"])
     return canon, uri
+
+
+def parse_index(payload: Dict[str, Any], opt: Options) -> tuple:
+    """``payload.index`` in canonical form, ``(clusters or None, nprobe or None, train_iterations)``: everything
+    about it that can be refused without the corpus (:func:`resolve_index` does the rest)."""
+    ix = payload["index"]
+    if not isinstance(ix, dict) or ix.get("type") != "ivf" or not set(ix) <= set(INDEX_KEYS):
+        raise ValueError(IVF_ERRORS["index"])
+
+    def integer(key, hi, default):
+        if key not in ix:
+            return default
+        v = ix[key]
+        if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= hi:
+            raise ValueError(IVF_ERRORS["index"])
+        return v
+
+    canon = (integer("clusters", MAX_CLUSTERS, None), integer("nprobe", MAX_NPROBE, None),
+             integer("train_iterations", MAX_TRAIN_ITERATIONS, 10))
+    if canon[0] is not None and canon[1] is not None and canon[1] > canon[0]:
+        raise ValueError(IVF_ERRORS["index"])
+    if "corpus_uri" not in payload:
+        raise ValueError(IVF_ERRORS["index_corpus"])
+    if opt.metric != "cosine":
+        raise ValueError(IVF_ERRORS["index_metric"])
+    if opt.corpus_dtype != "float32":
+        raise ValueError(IVF_ERRORS["index_f16"])
+    if "filter" in payload:
+        raise ValueError(IVF_ERRORS["index_filter"])
+    return canon
+
+
+def resolve_index(index: tuple, total: int) -> tuple:
+    """(clusters, nprobe, train_iterations) of a canonical ``index`` for a corpus of ``total`` rows: the
+    defaults ``ceil(sqrt(total))`` (clamped to ``[1, min(4096, total)]``) and ``min(8, clusters)``, and the
+    bounds that need the corpus."""
+    from agent_tpu_amd.runtime.ivf import default_clusters
+
+    clusters, nprobe, t = index
+    if clusters is None:
+        clusters = default_clusters(total)
+    elif clusters > total:
+        raise ValueError(IVF_ERRORS["index"])
+    if nprobe is None:
+        nprobe = min(8, clusters)
+    elif nprobe > clusters:
+        raise ValueError(IVF_ERRORS["index"])
+    return clusters, nprobe, t
 
 
 def options(payload: Dict[str, Any]) -> Options:
@@ -160,6 +226,8 @@ def check_payload(payload: Dict[str, Any]) -> Options:
     if "filter" in payload:  # a job without one keeps its Options, its code path and its result keys
         flt, labels_uri = parse_filter(payload)
         opt = opt._replace(filter=flt, labels_uri=labels_uri)
+    if "index" in payload:  # likewise: a job without one is untouched
+        opt = opt._replace(index=parse_index(payload, opt))
     return opt
 
 
@@ -254,6 +322,56 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
     return s[:, :kk], i[:, :kk], total, cached, filter_rows
 
 
+def search_queries_ivf(device, qvecs, payload: Dict[str, Any], top_k: int, index: tuple, rank: int, ws: int):
+    """:func:`search_queries` through an IVF index (``runtime/ivf.py``): every rank probes with the same global
+    centroids and searches its own cluster-sorted slice with ``id_base`` = the slice start; the lists, already
+    padded to ``top_k``, are all-gathered and merged as the exact ones are. The union of the ranks' probed rows
+    is the probed clusters of the whole corpus, so the result has the same bits for every world size. The build
+    contains collectives: the ranks' hit / miss flags travel with the error exchange, and all rebuild if any
+    missed. -> (scores, ids on the host, padded to ``top_k``; corpus rows; index_cached; the result's ``index``
+    dict) on rank 0, None elsewhere."""
+    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
+    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
+    from agent_tpu_amd.runtime import ivf
+    from agent_tpu_amd.runtime import search as rs
+
+    exc, total, key, hit, corpus, s_r = None, 0, None, None, None, 0
+    nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
+    try:
+        total, cdim = rs.corpus_shape(payload["corpus_uri"])
+        if cdim != dim:
+            raise ValueError(ERRORS["dim"])
+        clusters, nprobe, t = resolve_index(index, total)
+        s_r, n_r = split_range(0, total, ws, rank)
+        key, hit, corpus = ivf.open_index(payload["corpus_uri"], s_r, n_r, device, clusters, t)
+    except Exception as e:
+        exc = e
+    hits = exchange_errors(exc, hit is not None)  # raises on every rank together
+    if all(hits):
+        idx = hit
+    else:  # a collective: every rank builds, a rank that had the entry from its own rows
+        x = corpus.vectors if corpus is not None else ivf.original_rows(hit)
+        idx = ivf.build_index(key, x, clusters, t, rank, ws, s_r, total)
+    s, i = None, None
+    try:
+        maybe_inject_fault("search")
+        s, i, _ = ivf.search(qvecs, idx, top_k, nprobe, id_base=s_r)
+    except Exception as e:
+        exc = e
+    counts = exchange_errors(exc, nq if s is not None else 0)
+    s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
+    if rank != 0:
+        return None
+    s, i = s.cpu(), i.cpu()
+    if ws > 1:  # as search_queries: every query's ws lists side by side -> merged; the padding sorts last
+        s = s.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        s, i = rs.merge_topk(s, i, top_k)
+    info = {"type": "ivf", "clusters": clusters, "nprobe": nprobe, "train_iterations": idx.iterations,
+            "converged": idx.converged}
+    return s, i, total, idx.cached, info
+
+
 def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str]], metric: str, pooling: str):
     """``[nq, dim]`` fp32 query vectors: the model's embeddings of ``queries``, or ``query_vectors``
     on the device (normalised there for cosine)."""
@@ -269,13 +387,18 @@ def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str
 
 
 def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim: int, cached: Optional[bool],
-           ws: int, filter_rows: Optional[int] = None) -> Dict[str, Any]:
+           ws: int, filter_rows: Optional[int] = None, index_info: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """One job's result from its rows of the merged lists (rank 0): the first ``top_k`` entries (with
     a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host.
-    ``filter_rows``: the corpus rows that passed the job's filter (None: no filter)."""
+    ``filter_rows``: the corpus rows that passed the job's filter (None: no filter). ``index_info``: the
+    ``index`` key of a job with an index (None: no index); its lists end where the padding begins."""
     opt = options(payload)
     kk = min(top_k, total if filter_rows is None else filter_rows)
     ids_l, sc_l = ids[:, :kk].tolist(), scores[:, :kk].tolist()
+    if index_info is not None:  # a query whose probed clusters hold fewer than top_k rows: a shorter list
+        keep = [sum(1 for x in row if x != PAD_ID) for row in ids_l]
+        ids_l = [row[:m] for row, m in zip(ids_l, keep)]
+        sc_l = [row[:m] for row, m in zip(sc_l, keep)]
     if opt.min_score is not None:
         keep = [[j for j, v in enumerate(row) if v >= opt.min_score] for row in sc_l]
         ids_l = [[row[j] for j in ks] for row, ks in zip(ids_l, keep)]
@@ -295,6 +418,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         out["corpus_dtype"] = opt.corpus_dtype
     if filter_rows is not None:
         out["filter_rows"] = int(filter_rows)
+    if index_info is not None:
+        out["index"] = dict(index_info)
     out.update(ids=ids_l, scores=sc_l)
     return out
 
@@ -325,6 +450,12 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         qv = torch.zeros((0, dim), dtype=torch.float32) if h is not None else None
         if qv is None:
             raise ValueError(ERRORS["query_vectors"])
+    if opt.index is not None:  # its own path, so that a job without an index stays as it was
+        got = search_queries_ivf(device, qv, payload, opt.top_k, opt.index, rank, ws)
+        if got is None:
+            return None
+        s, i, total, cached, info = got
+        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, index_info=info)
     got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
                          opt.filter, opt.labels_uri)
     if got is None:
@@ -360,18 +491,23 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 import torch
 
                 qv = torch.cat([h.engine.embed_texts(ts, key.pooling, key.metric == "cosine").emb for _, _, ts in jobs])
-            got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
-                                 key.filter, key.labels_uri)
+            if key.index is not None:  # the group shares the canonical index, nprobe included
+                got = search_queries_ivf(device, qv, first, K, key.index, rank, ws)
+                got = None if got is None else got[:4] + (None, got[4])
+            else:
+                got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
+                                     key.filter, key.labels_uri)
+                got = None if got is None else got + (None,)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
                 out[n] = ("err", exc)
             return out if rank == 0 else None
         if got is not None:
-            s, i, total, cached, filter_rows = got
+            s, i, total, cached, filter_rows, info = got
             pos = 0
             for n, opt, ts in jobs:
                 out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
-                                       int(qv.shape[1]), cached, ws, filter_rows))
+                                       int(qv.shape[1]), cached, ws, filter_rows, info))
                 pos += len(ts)
     return out if rank == 0 else None
 
@@ -379,8 +515,8 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 @register_batch_op("map_search")
 def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``queries`` + ``corpus_uri`` jobs that share (model_path, pooling, metric,
-    corpus_uri, corpus_dtype, and with a ``filter`` its canonical form and label file) go to the
-    device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
+    corpus_uri, corpus_dtype, with a ``filter`` its canonical form and label file, and with an ``index`` its
+    canonical (clusters, train_iterations) and nprobe) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
     single-job path."""
 
     def key(p):
@@ -388,6 +524,9 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
             raise KeyError("queries")  # not batchable
         opt = check_payload(p)
         group = p.get("model_path"), opt.pooling, opt.metric, p["corpus_uri"], opt.corpus_dtype
+        if opt.index is not None:  # (clusters, train_iterations) name the index; jobs that differ in nprobe probe
+            clusters, nprobe, t = opt.index  # other rows per query, so they stay separate groups
+            return group + ("ivf", clusters, t, nprobe)
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
     return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
