@@ -553,6 +553,14 @@ PYBIND11_MODULE(_atpu, m) {
                          uintptr_t stream) {
     group_topk(P<const float>(scores), P<const int32_t>(goff), P<int32_t>(idx), P<float>(val), rows, Q, k, S(stream));
   });
+  m.def("token_unit", [](uintptr_t x, uintptr_t out, int M, int Pd, int is_bf16, uintptr_t stream) {
+    token_unit(P<const void>(x), P<float>(out), M, Pd, is_bf16, S(stream));
+  });
+  m.def("maxsim", [](uintptr_t qv, uintptr_t lens_q, uintptr_t dv, uintptr_t lens_d, uintptr_t qidx, uintptr_t didx,
+                     uintptr_t scores, int n, int Qn, int Dn, int Sq, int Pd, uintptr_t stream) {
+    maxsim(P<const float>(qv), P<const int32_t>(lens_q), P<const float>(dv), P<const int32_t>(lens_d),
+           P<const int32_t>(qidx), P<const int32_t>(didx), P<float>(scores), n, Qn, Dn, Sq, Pd, S(stream));
+  });
   m.def("premise_assemble",
         [](uintptr_t ids_t, uintptr_t lens_t, uintptr_t ids_h, uintptr_t lens_h, uintptr_t tidx, uintptr_t hidx,
            uintptr_t ids, uintptr_t type_ids, uintptr_t lens, int rows, int T, int Hn, int Sq, int mh, int cls, int sep,

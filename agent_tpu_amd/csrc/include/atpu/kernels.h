@@ -410,6 +410,20 @@ void pair_assemble(const int32_t* ids_q, const int32_t* lens_q, const int32_t* i
 void group_topk(const float* scores, const int32_t* goff, int32_t* idx, float* val, int P, int Q, int k,
                 hipStream_t stream);
 
+// ------------------------------------------------ late interaction (maxsim.hip)
+// out [M, P] fp32 = the rows of x [M, P] (bf16 when is_bf16, else fp32) divided by max(||row||_2, 1e-12)
+// (pool_embed's normalisation); the squares are summed in an order that depends on P alone.
+// P % 64 == 0 in [64, 1024]; M == 0: no launch.
+void token_unit(const void* x, float* out, int M, int P, int is_bf16, hipStream_t stream);
+// scores [n]: pair p = (q = clamp(qidx[p], 0, Qn-1), d = clamp(didx[p], 0, Dn-1)) of the unit token
+// vectors qv [Qn, S, P] / dv [Dn, S, P] (fp32, 16-byte aligned) gets
+//   sum_{i < len_q} max_{j < len_d} <qv[q, i], dv[d, j]>      (lens clamped into [1, S])
+// with every dot product in exact fp32 in sim_topk's k order, the max by select (tokens >= len never
+// enter, whatever they hold) and the sum in fp32 in increasing i: a function of the pair's own rows
+// alone. P % 64 == 0 in [64, 1024]; n == 0: no launch. A NaN in a live dot product: undefined.
+void maxsim(const float* qv, const int32_t* lens_q, const float* dv, const int32_t* lens_d, const int32_t* qidx,
+            const int32_t* didx, float* scores, int n, int Qn, int Dn, int S, int P, hipStream_t stream);
+
 // ------------------------------------------- zero-shot classification (zeroshot.hip)
 // Premise-first pair rows "atpu-premise v1" (agent_tpu_amd/tokenizer.py premise_rows is the twin): row r
 // with text row t = clamp(tidx[r], 0, T-1) and hypothesis row h = clamp(hidx[r], 0, Hn-1) becomes

@@ -43,6 +43,11 @@ class BertConfig:
     qa_head: bool = False  # a span head (HF BertForQuestionAnswering qa_outputs) after the classifier
     tag_labels: int = 0  # > 0: a token classification head of that many labels after the other heads
     mlm_head: bool = False  # a masked-LM head (HF BertForMaskedLM cls.predictions, decoder tied to emb.word) last
+    late_dim: int = 0  # > 0: a bias-free late-interaction projection [late_dim, H] (ColBERT's linear) after every other head
+
+    def __post_init__(self):
+        if self.late_dim < 0 or self.late_dim % 64 != 0:
+            raise ValueError("late_dim must be a multiple of 64")
 
     @property
     def head_dim(self) -> int:
@@ -59,6 +64,7 @@ class BertConfig:
             head += self.tag_labels * H + self.tag_labels
         if self.mlm_head:
             head += H * H + 3 * H + self.vocab_size
+        head += self.late_dim * H
         return emb + L * layer + head
 
     def flops_per_row_executed(self, seq_len: int, cls_only_last: bool = True,
@@ -142,6 +148,8 @@ def param_specs(cfg: BertConfig):
         yield "mlm_ln_g", (H,), f32
         yield "mlm_ln_b", (H,), f32
         yield "mlm_out_b", (cfg.vocab_size,), f32
+    if cfg.late_dim > 0:  # after every other head: packs without it keep their layout
+        yield "late_w", (cfg.late_dim, H), bf
 
 
 def init_random(cfg: BertConfig, seed: int = 0, std: float = 0.02, bias_std: float = 0.0,
@@ -175,11 +183,14 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor], head: str =
     tensors the dict does not have stay zero. ``head="token"``: a ``BertForTokenClassification`` dict
     (no pooler), whose ``classifier.*`` is the tag head (``cfg.tag_labels``), not the row classifier.
     ``head="mlm"``: a ``BertForMaskedLM`` dict (``cls.predictions.*``; ``cfg.mlm_head``); its decoder must be
-    tied to the word embeddings."""
-    if head not in ("sequence", "token", "mlm"):
-        raise ValueError("head must be 'sequence', 'token' or 'mlm'")
+    tied to the word embeddings. ``head="late"``: a ColBERT dict, a ``BertModel`` under ``bert.`` plus the
+    bias-free projection ``linear.weight`` ``[late_dim, H]`` (``cfg.late_dim``)."""
+    if head not in ("sequence", "token", "mlm", "late"):
+        raise ValueError("head must be 'sequence', 'token', 'mlm' or 'late'")
     if head == "mlm" and not cfg.mlm_head:
         raise ValueError("head 'mlm' needs a config with mlm_head")
+    if head == "late" and cfg.late_dim <= 0:
+        raise ValueError("head 'late' needs a config with late_dim")
     pack = ParamPack(param_specs(cfg))
     if "embeddings.word_embeddings.weight" in sd and "bert.embeddings.word_embeddings.weight" not in sd:
         sd = {"bert." + k: v for k, v in sd.items()}
@@ -223,6 +234,8 @@ def from_hf_state_dict(cfg: BertConfig, sd: Dict[str, torch.Tensor], head: str =
         put("mlm_ln_g", sd[c + "transform.LayerNorm.weight"])
         put("mlm_ln_b", sd[c + "transform.LayerNorm.bias"])
         put("mlm_out_b", sd[c + "bias"])
+    if head == "late":
+        put("late_w", sd["linear.weight"])
     return pack
 
 
@@ -566,6 +579,18 @@ class BertClassifier:
                                   normalize=normalize)
         h = self.encode(ids, lens, type_ids, cls_only_last=False)
         return ops.pool_embed(h, lens, B, normalize=normalize)
+
+    # ------------------------------------------------------------ late interaction
+    def token_vectors(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Unit token vectors ``[B*S, P]`` fp32 for late-interaction scoring (``ops.maxsim``): the last hidden
+        states (every layer in full, the final LayerNorm applied), through the bias-free ``late_w``
+        projection when the model has one (``P = late_dim``, else ``P = H``), every row L2-normalised by
+        ``ops.token_unit``. Rows of padding positions are normalised like any other; ``maxsim`` ignores them."""
+        h = self.encode(ids, lens, type_ids, cls_only_last=False)
+        if self.cfg.late_dim > 0:
+            h = ops.linear(h, self.p["late_w"], out_f32=True)
+        return ops.token_unit(h.contiguous(), out=out)
 
     # ------------------------------------------------------------ question answering
     def span_inputs(self) -> Dict[str, torch.Tensor]:

@@ -19,10 +19,10 @@ tasks (C2 all-gather of embeddings), ``map_search`` (C2 all-gather of
 per-rank top-k lists, merged on rank 0), ``map_cluster`` (C3 integer
 all-reduce of the centroid sums per iteration), ``map_dedup`` (C2 ragged
 all-gather of the join's pairs) and, from the :data:`BATCHED_OPS`
-table, the ``map_rerank``, ``map_answer``, ``map_tag``, ``map_fill`` and
-``map_zero_shot`` tasks with their ``_batch`` forms (C2 all-gather of pair
-scores, span rows, entity records, mask candidates or NLI logits, ranked or
-mapped on rank 0).
+table, the ``map_rerank``, ``map_answer``, ``map_tag``, ``map_fill``,
+``map_zero_shot`` and ``map_maxsim`` tasks with their ``_batch`` forms (C2
+all-gather of pair scores, span rows, entity records, mask candidates, NLI
+logits or late-interaction scores, ranked or mapped on rank 0).
 """
 from __future__ import annotations
 
@@ -592,7 +592,7 @@ def dedup_task(payload: Dict[str, Any]) -> Any:
     return md.dedup_one(payload, rank, ws)
 
 
-# ---------------------------- map_rerank, map_answer, map_tag, map_fill, map_zero_shot
+# ---------------------------- map_rerank, map_answer, map_tag, map_fill, map_zero_shot, map_maxsim
 #: task name -> (``ops`` module, its batch function); every op has a single-job task under its own name
 #: and a ``_batch`` task for the jobs of one lease that share its group key
 BATCHED_OPS = {"map_rerank": ("map_rerank", "rerank_batch"), "map_rerank_batch": ("map_rerank", "rerank_batch"),
@@ -600,7 +600,8 @@ BATCHED_OPS = {"map_rerank": ("map_rerank", "rerank_batch"), "map_rerank_batch":
                "map_tag": ("map_tag", "tag_batch"), "map_tag_batch": ("map_tag", "tag_batch"),
                "map_fill": ("map_fill", "fill_batch"), "map_fill_batch": ("map_fill", "fill_batch"),
                "map_zero_shot": ("map_zero_shot", "zero_shot_batch"),
-               "map_zero_shot_batch": ("map_zero_shot", "zero_shot_batch")}
+               "map_zero_shot_batch": ("map_zero_shot", "zero_shot_batch"),
+               "map_maxsim": ("map_maxsim", "maxsim_batch"), "map_maxsim_batch": ("map_maxsim", "maxsim_batch")}
 
 
 def _register_batched(name: str, module: str, batch_fn: str) -> None:

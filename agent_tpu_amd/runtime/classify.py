@@ -1390,6 +1390,119 @@ class ClassifyEngine:
         scores = self.score_pairs(queries, passages, goff, max_query_tokens, label)
         return self.rank_scores(scores, goff, top_k, activation)
 
+    # ------------------------------------------------------ late interaction (map_maxsim)
+    # ColBERT scoring: the encoder reads every query and every passage once, alone, and keeps one unit
+    # vector per token (model.token_vectors); a pair's score is ops.maxsim of its two rows. All queries
+    # are encoded first, in chunks of at most B rows through the ("maxsim", bucket) graphs (tokenize,
+    # token_vectors), and stay resident as qv [Q, S, P] with their lengths. The passages then stream in
+    # chunks of at most B through the same graphs (the bucket is that of the rows staged, so 32 queries
+    # cost a 32-row step whatever the passage chunks are), and one maxsim launch per chunk scores the
+    # chunk's pairs into the result. Pair form: pair p is passage p with its own query (qidx through
+    # the re-ranker's pinned index row, didx = arange). Shared form: every query against every passage
+    # of the chunk, Q * bucket pairs whose index rows are built on the device once per (Q, bucket).
+    @property
+    def late_dim(self) -> int:
+        """The width ``P`` of the token vectors: the late head's, or the hidden size without one."""
+        return self.cfg.late_dim or self.cfg.hidden
+
+    def _token_vector_step(self, bucket: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bucket)
+        return self.model.token_vectors(self.ids_s[0][:bucket], self.lens_s[0][:bucket]), self.lens_s[0][:bucket]
+
+    def _token_vector_chunks(self, rows: Sequence):
+        """Yields ``(c0, m, bucket, tv [bucket * S, P] fp32, lens [bucket] int32)`` per chunk of at most ``B``
+        rows; rows ``m .. bucket - 1`` are empty strings. On the GPU ``tv`` / ``lens`` are a graph's static
+        outputs, valid until the next chunk: the consumer's work on them is ordered before the event after
+        which the pinned rows (and the graph) are used again."""
+        cuda = self.device.type == "cuda"
+        free = None
+        for c0 in range(0, len(rows), self.B):
+            chunk = pack_rows(self._encode_rows(rows[c0:c0 + self.B]))
+            m = min(self.B, len(rows) - c0)
+            if not cuda:
+                ids, lens = self._tokenize(torch.from_numpy(chunk[0]), torch.from_numpy(chunk[1]))
+                # one row per call: the PyTorch reference's fp32 sums depend on the rows batched together,
+                # and a row's vectors must not (the kernels' are batch-invariant by construction)
+                tv = torch.cat([self.model.token_vectors(ids[i:i + 1], lens[i:i + 1]) for i in range(m)])
+                yield c0, m, m, tv, lens
+                continue
+            if free is not None:
+                free.synchronize()
+            bk = self._stage_texts(chunk, m)
+            tv, lens = self._replay(("maxsim", bk), lambda: self._token_vector_step(bk))
+            yield c0, m, bk, tv, lens
+            free = torch.cuda.Event()
+            free.record()
+        if free is not None:
+            free.synchronize()  # the pinned rows are free for the next call, whichever form it is
+
+    def _shared_index(self, Q: int, bucket: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(qidx, didx)`` int32 ``[Q * bucket]`` of every query against every row of a chunk, query-major."""
+        cache = self.__dict__.setdefault("_ms_idx", {})
+        if (Q, bucket) not in cache:
+            if len(cache) >= 16:
+                cache.clear()
+            q = torch.arange(Q, dtype=torch.int32, device=self.device).repeat_interleave(bucket)
+            d = torch.arange(bucket, dtype=torch.int32, device=self.device).repeat(Q)
+            cache[(Q, bucket)] = (q.contiguous(), d.contiguous())
+        return cache[(Q, bucket)]
+
+    def maxsim_scores(self, queries: Sequence, passages: Sequence, goff: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Late-interaction scores, fp32, left on the engine's device (a DP caller all-gathers them). With
+        ``goff`` (pair form) ``[P]``: ``passages`` is the flat list of all candidates, query ``q`` owning rows
+        ``goff[q] .. goff[q + 1] - 1``, as in :meth:`score_pairs`. With ``goff=None`` (shared form) ``[Q, N]``:
+        every query against every passage. ``self.maxsim_lens_q`` holds the queries' token counts, ``[Q]``
+        int32 on the device. A score depends on its own two texts only: not on the chunking or the form."""
+        Q, N = len(queries), len(passages)
+        S, P, dev = self.S, self.late_dim, self.device
+        if goff is not None:
+            goff = self._check_goff(goff, Q, N)
+        if not ops.maxsim_ok(P):
+            raise ValueError("token vectors must have a width that is a multiple of 64 in [64, 1024]")
+        if Q * S * P * 4 > float(os.getenv("MAXSIM_QUERY_GB", "4")) * 2**30:
+            raise ValueError("too many queries for the token-vector buffer")
+        out = torch.empty((N,) if goff is not None else (Q, N), dtype=torch.float32, device=dev)
+        qv = torch.empty((Q, S, P), dtype=torch.float32, device=dev)
+        lens_q = torch.ones(Q, dtype=torch.int32, device=dev)
+        self.maxsim_lens_q = lens_q
+        for c0, m, _, tv, lens in self._token_vector_chunks(queries):
+            qv[c0:c0 + m].copy_(tv.view(-1, S, P)[:m])
+            lens_q[c0:c0 + m].copy_(lens[:m])
+        if Q == 0 or N == 0:
+            return out
+        cuda = dev.type == "cuda"
+        if goff is not None:
+            qid = np.repeat(np.arange(Q, dtype=np.int32), np.diff(np.asarray(goff, dtype=np.int64)))  # row -> query
+            r = self._rerank_bufs()
+            arange = torch.arange(self.B, dtype=torch.int32, device=dev)
+        for c0, m, bk, tv, lens in self._token_vector_chunks(passages):
+            dv = tv.view(-1, S, P)
+            if goff is None:
+                qidx, didx = self._shared_index(Q, bk)
+                sc = ops.maxsim(qv, lens_q, dv, lens, qidx, didx)
+                out[:, c0:c0 + m].copy_(sc.view(Q, bk)[:, :m])
+                continue
+            if cuda:  # the previous chunk's copy out of the pinned row completed before this chunk was staged
+                r["pin_qidx"][:m].copy_(torch.from_numpy(qid[c0:c0 + m]))
+                r["qidx"][:m].copy_(r["pin_qidx"][:m], non_blocking=True)
+                qidx = r["qidx"][:m]
+            else:
+                qidx = torch.from_numpy(qid[c0:c0 + m].copy())
+            ops.maxsim(qv, lens_q, dv, lens, qidx, arange[:m], out=out[c0:c0 + m])
+        return out
+
+    def maxsim_rank(self, queries: Sequence, passages: Sequence, goff: Optional[Sequence[int]] = None,
+                    top_k: int = 10) -> RerankResult:
+        """:meth:`maxsim_scores`, then :meth:`rank_scores`: each query's own passages (pair form) or all of
+        them (shared form: ``goff = [0, N, 2N, ...]`` over the flattened ``[Q * N]``) ranked; ``index`` is the
+        position in the query's list, or in ``passages``."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        scores = self.maxsim_scores(queries, passages, goff)
+        if goff is None:
+            goff = [q * len(passages) for q in range(len(queries) + 1)]
+        return self.rank_scores(scores.reshape(-1), goff, top_k)
+
     # ------------------------------------------------------ zero-shot classification (map_zero_shot)
     # An NLI model reads every text with one hypothesis per candidate label as ``[CLS] text [SEP]
     # hypothesis [SEP]`` (``ops.premise_assemble``). Neither segment is one row per pair: per chunk of at

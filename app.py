@@ -247,9 +247,9 @@ METRICS = Metrics()
 
 # --------------------------------------------------------------- profile
 GPU_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_cluster", "map_dedup", "map_rerank", "map_answer", "map_tag", "map_fill",
-           "map_zero_shot", "map_summarize", "risk_accumulate"}
+           "map_zero_shot", "map_maxsim", "map_summarize", "risk_accumulate"}
 BATCH_OPS = {"map_classify", "map_classify_tpu", "map_embed", "map_search", "map_rerank", "map_answer", "map_tag", "map_fill",
-             "map_zero_shot", "map_summarize"}
+             "map_zero_shot", "map_maxsim", "map_summarize"}
 
 
 def gpu_health(caps: List[str]) -> Optional[Dict[str, Any]]:

@@ -63,6 +63,7 @@ OP_TO_MODULE: Dict[str, str] = {
     "map_tag": "map_tag",
     "map_fill": "map_fill",
     "map_zero_shot": "map_zero_shot",
+    "map_maxsim": "map_maxsim",
     "map_summarize": "map_summarize",
     # outbound side effects (opt-in only)
     "trigger_oracle": "trigger_oracle",

@@ -30,6 +30,9 @@ default), ``pool_*`` / ``cls_*`` are optional, and ``map_classify`` / ``map_rera
 ``mlm_ln_b`` / ``mlm_out_b`` (the masked-LM head ``map_fill`` needs; the decoder is the word embeddings),
 ``pool_*`` / ``cls_*`` are optional, and the other head ops refuse it. ``?mlm=1`` on a preset adds a
 random-init MLM head.
+``"head": "late"`` with ``"late_dim": N`` marks a ColBERT export: the file holds the bias-free projection
+``late_w [N, H]`` (the late-interaction head ``map_maxsim`` scores with), ``pool_*`` / ``cls_*`` are optional, and
+the other head ops refuse it. ``?late=N`` (a multiple of 64) on a preset adds a random-init projection.
 ``?nli=1`` on a preset makes it an NLI classifier for ``map_zero_shot``: 3 labels unless ``labels=`` says otherwise,
 entailment id 2 and contradiction id 0 (the MNLI order). A classifier json may name its labels in
 ``"nli_labels": [...]`` (one per label): the entailment id is the first name that starts with "entail", the
@@ -76,6 +79,9 @@ class ModelSpec:
     # an NLI classifier: (entailment_id, contradiction_id) ("?nli=1": (2, 0), or "nli_labels" in the json); None:
     # map_zero_shot takes (num_labels - 1, 0) unless the payload names them
     nli: Optional[Tuple[int, int]] = None
+    # the width of a late-interaction projection ("?late=N", or "head": "late" with "late_dim": N in the json,
+    # which clears ``head``): map_maxsim scores with it; 0: map_maxsim takes the hidden states themselves
+    late: int = 0
 
 
 def _flag(value: Any) -> bool:
@@ -88,6 +94,13 @@ def _tags(value: Any) -> int:
     n = int(value)
     if not 0 <= n <= 64:
         raise ValueError("a tag head has 1 to 64 labels")
+    return n
+
+
+def _late(value: Any) -> int:
+    n = int(value)
+    if n < 0 or n % 64 != 0 or n > 1024:
+        raise ValueError("a late-interaction head has a width that is a multiple of 64, at most 1024")
     return n
 
 
@@ -120,7 +133,7 @@ def parse_spec(path: str) -> ModelSpec:
                          int(q.get("seed", os.getenv("MODEL_SEED", "0"))), batch, seq, quant=quant,
                          vocab=vocab, lowercase=True if lowercase is None else lowercase,
                          qa=_flag(q.get("qa", "0")), tags=_tags(q.get("tags", "0")),
-                         mlm=_flag(q.get("mlm", "0")), nli=(2, 0) if nli else None)
+                         mlm=_flag(q.get("mlm", "0")), nli=(2, 0) if nli else None, late=_late(q.get("late", "0")))
     if base.endswith(".safetensors"):
         if not os.path.exists(base):
             raise FileNotFoundError(f"GPU model not found: {base}")
@@ -142,11 +155,16 @@ def parse_spec(path: str) -> ModelSpec:
         nli = None
         if meta.get("nli_labels") is not None:
             nli = nli_ids_of(meta["nli_labels"], int(meta.get("num_labels", 2)), base + ".json")
+        late = 0
+        if head == "late":
+            late = _late(meta.get("late_dim", 0))
+            if late <= 0:
+                raise ValueError(f'{base}.json: "head": "late" needs "late_dim": a multiple of 64')
         return ModelSpec(path, meta.get("preset", DEFAULT_MODEL), int(meta.get("num_labels", 2)), 0, batch, seq,
                          file=base, quant=quant, vocab=vocab, lowercase=lowercase,
-                         head=head not in ("none", "qa", "token", "mlm"), qa=head == "qa",
+                         head=head not in ("none", "qa", "token", "mlm", "late"), qa=head == "qa",
                          tags=len(names) if names else 0, tag_names=names, tag_outside=outside, mlm=head == "mlm",
-                         nli=nli)
+                         nli=nli, late=late)
     raise FileNotFoundError(f"GPU model not found: {path}")
 
 
@@ -236,7 +254,7 @@ def _build_handle(model_path: str, device) -> GpuHandle:
     def local():
         spec = parse_spec(model_path)
         cfg = config_for(spec.preset, num_labels=spec.labels, qa_head=spec.qa, tag_labels=spec.tags,
-                         mlm_head=spec.mlm)
+                         mlm_head=spec.mlm, late_dim=spec.late)
         box.update(spec=spec, cfg=cfg)
         # the vocabulary is read and its table built on every rank (same file, same node: no
         # broadcast), before the weights, so a missing or bad file on any rank fails the load on all
