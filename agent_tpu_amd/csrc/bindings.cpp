@@ -561,6 +561,13 @@ PYBIND11_MODULE(_atpu, m) {
     maxsim(P<const float>(qv), P<const int32_t>(lens_q), P<const float>(dv), P<const int32_t>(lens_d),
            P<const int32_t>(qidx), P<const int32_t>(didx), P<float>(scores), n, Qn, Dn, Sq, Pd, S(stream));
   });
+  m.def("maxsim_index", [](uintptr_t qv, uintptr_t lens_q, uintptr_t tok, uintptr_t off, uintptr_t pidx, uintptr_t qoff,
+                           uintptr_t qsel, uintptr_t out, int Qn, int Sq, int Pd, int64_t T, int N, int M, int E, int is_f16,
+                           uintptr_t stream) {
+    maxsim_index(P<const float>(qv), P<const int32_t>(lens_q), P<const void>(tok), P<const int64_t>(off),
+                 P<const int32_t>(pidx), P<const int32_t>(qoff), P<const int32_t>(qsel), P<float>(out), Qn, Sq, Pd, T, N, M,
+                 E, is_f16, S(stream));
+  });
   m.def("premise_assemble",
         [](uintptr_t ids_t, uintptr_t lens_t, uintptr_t ids_h, uintptr_t lens_h, uintptr_t tidx, uintptr_t hidx,
            uintptr_t ids, uintptr_t type_ids, uintptr_t lens, int rows, int T, int Hn, int Sq, int mh, int cls, int sep,

@@ -424,6 +424,19 @@ void token_unit(const void* x, float* out, int M, int P, int is_bf16, hipStream_
 void maxsim(const float* qv, const int32_t* lens_q, const float* dv, const int32_t* lens_d, const int32_t* qidx,
             const int32_t* didx, float* scores, int n, int Qn, int Dn, int S, int P, hipStream_t stream);
 
+// ---------------------------------- late interaction over a resident index (maxsim_index.hip)
+// The same score against a packed index: tok [T, P] (fp16 when is_f16, else fp32) holds the live unit token
+// vectors of N passages back to back, passage p being rows off[p] .. off[p + 1] - 1 (off [N + 1] int64). Work
+// item m is passage pidx[m] (m itself when pidx is null, M == N). All form (qoff and qsel null): out [Qn, M],
+// every query against every item. List form: out [E], entry e in [qoff[m], qoff[m + 1]) is query qsel[e]
+// against item m; an empty range is valid. One workgroup per item keeps the passage in LDS and loops over
+// its queries. Exact fp32 dot products in a k order that depends on P and the dtype alone (fp32: maxsim's,
+// the same bits); pidx, qsel, qoff, lens_q and the offsets are clamped before they form an address.
+// P % 64 == 0 in [64, 1024]; M == 0: no launch.
+void maxsim_index(const float* qv, const int32_t* lens_q, const void* tok, const int64_t* off, const int32_t* pidx,
+                  const int32_t* qoff, const int32_t* qsel, float* out, int Qn, int S, int P, int64_t T, int N, int M, int E,
+                  int is_f16, hipStream_t stream);
+
 // ------------------------------------------- zero-shot classification (zeroshot.hip)
 // Premise-first pair rows "atpu-premise v1" (agent_tpu_amd/tokenizer.py premise_rows is the twin): row r
 // with text row t = clamp(tidx[r], 0, T-1) and hypothesis row h = clamp(hidx[r], 0, Hn-1) becomes

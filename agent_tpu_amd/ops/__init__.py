@@ -30,7 +30,8 @@ from .dedup import (sim_join, sim_join_ok, sim_join_ref, sort_pairs, cc_min_labe
 from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_layernorm  # noqa: F401
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .rerank import pair_assemble, pair_assemble_ref, group_topk, group_topk_ref  # noqa: F401
-from .maxsim import token_unit, token_unit_ref, maxsim, maxsim_ref, maxsim_ok  # noqa: F401
+from .maxsim import (token_unit, token_unit_ref, maxsim, maxsim_ref, maxsim_ok, maxsim_index,  # noqa: F401
+                     maxsim_index_ref)
 from .span import span_topk, span_topk_ok, span_topk_ref, span_logits_ref, span_select_ref  # noqa: F401
 from .window import window_assemble, window_assemble_ref, window_best, window_best_ref  # noqa: F401
 from .tag import (tag_entities, tag_ok, tag_logits_ref, tag_select_ref, tag_group_ref, tag_tables,  # noqa: F401

@@ -1447,6 +1447,18 @@ class ClassifyEngine:
             cache[(Q, bucket)] = (q.contiguous(), d.contiguous())
         return cache[(Q, bucket)]
 
+    def _maxsim_queries(self, queries: Sequence) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(qv [Q, S, P] fp32, lens_q [Q] int32)`` of the queries, resident on the device; ``lens_q`` is also
+        ``self.maxsim_lens_q``."""
+        Q, S, P, dev = len(queries), self.S, self.late_dim, self.device
+        qv = torch.empty((Q, S, P), dtype=torch.float32, device=dev)
+        lens_q = torch.ones(Q, dtype=torch.int32, device=dev)
+        self.maxsim_lens_q = lens_q
+        for c0, m, _, tv, lens in self._token_vector_chunks(queries):
+            qv[c0:c0 + m].copy_(tv.view(-1, S, P)[:m])
+            lens_q[c0:c0 + m].copy_(lens[:m])
+        return qv, lens_q
+
     def maxsim_scores(self, queries: Sequence, passages: Sequence, goff: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Late-interaction scores, fp32, left on the engine's device (a DP caller all-gathers them). With
         ``goff`` (pair form) ``[P]``: ``passages`` is the flat list of all candidates, query ``q`` owning rows
@@ -1462,12 +1474,7 @@ class ClassifyEngine:
         if Q * S * P * 4 > float(os.getenv("MAXSIM_QUERY_GB", "4")) * 2**30:
             raise ValueError("too many queries for the token-vector buffer")
         out = torch.empty((N,) if goff is not None else (Q, N), dtype=torch.float32, device=dev)
-        qv = torch.empty((Q, S, P), dtype=torch.float32, device=dev)
-        lens_q = torch.ones(Q, dtype=torch.int32, device=dev)
-        self.maxsim_lens_q = lens_q
-        for c0, m, _, tv, lens in self._token_vector_chunks(queries):
-            qv[c0:c0 + m].copy_(tv.view(-1, S, P)[:m])
-            lens_q[c0:c0 + m].copy_(lens[:m])
+        qv, lens_q = self._maxsim_queries(queries)
         if Q == 0 or N == 0:
             return out
         cuda = dev.type == "cuda"
@@ -1502,6 +1509,95 @@ class ClassifyEngine:
         if goff is None:
             goff = [q * len(passages) for q in range(len(queries) + 1)]
         return self.rank_scores(scores.reshape(-1), goff, top_k)
+
+    # ------------------------------------------- late interaction over a resident index (map_maxsim)
+    # The passages' token vectors are computed once (maxsim_build: the ("maxsim", bucket) graphs in chunks,
+    # the live rows of every chunk packed with plain PyTorch) and written as an index; a query call then
+    # encodes only the queries and scores them against the resident rows with ops.maxsim_index: one
+    # all-form launch over the rank's slice, or with per-query candidate lists one list-form launch over
+    # the passage-major work list that PyTorch ops on the device build from them.
+    def _check_late(self, Q: int = 0) -> None:
+        if not ops.maxsim_ok(self.late_dim):
+            raise ValueError("token vectors must have a width that is a multiple of 64 in [64, 1024]")
+        if Q * self.S * self.late_dim * 4 > float(os.getenv("MAXSIM_QUERY_GB", "4")) * 2**30:
+            raise ValueError("too many queries for the token-vector buffer")
+
+    def maxsim_build(self, passages: Sequence) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(tok [T, P] fp32, lens [N] int32)`` on the engine's device: the unit token vectors of the live
+        tokens of every passage back to back, the engine's own vectors (an index row has the bits of the
+        on-the-fly path), and every passage's token count."""
+        S, P, dev = self.S, self.late_dim, self.device
+        self._check_late()
+        pos = torch.arange(S, device=dev)
+        parts, counts = [], []
+        for _, m, _, tv, lens in self._token_vector_chunks(passages):
+            ln = lens[:m].clamp(1, S)
+            parts.append(tv.view(-1, S, P)[:m][pos[None, :] < ln[:, None]])  # a copy: the graph's output is reused
+            counts.append(ln.to(torch.int32))
+        if not parts:
+            return torch.empty((0, P), dtype=torch.float32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev)
+        return torch.cat(parts).contiguous(), torch.cat(counts).contiguous()
+
+    def _candidate_entries(self, candidates: Sequence[Sequence[int]], index) -> Tuple[torch.Tensor, ...]:
+        """The (query, passage) entries of the candidate lists that fall in the index's slice, passage-major:
+        ``(pidx [M], qoff [M + 1], qsel [E], col [E])``, ``col`` the entry's position in its query's list."""
+        dev = self.device
+        n = [len(c) for c in candidates]
+        pid = torch.tensor([int(p) for c in candidates for p in c], dtype=torch.int64).to(dev)
+        qid = torch.repeat_interleave(torch.arange(len(n)), torch.tensor(n, dtype=torch.int64)).to(dev)
+        col = torch.tensor([j for c in n for j in range(c)], dtype=torch.int64).to(dev)
+        keep = (pid >= index.start) & (pid < index.start + index.count)
+        pid, qid, col = pid[keep] - index.start, qid[keep], col[keep]
+        order = torch.sort(pid, stable=True).indices  # by passage; a passage's queries in input order
+        items, cnt = torch.unique_consecutive(pid[order], return_counts=True)
+        qoff = torch.zeros(int(items.numel()) + 1, dtype=torch.int32, device=dev)
+        qoff[1:] = torch.cumsum(cnt, 0).to(torch.int32)
+        return items.to(torch.int32).contiguous(), qoff, qid[order].to(torch.int32).contiguous(), col[order]
+
+    def maxsim_index_scores(self, queries: Sequence, index, candidates: Optional[Sequence[Sequence[int]]] = None
+                            ) -> torch.Tensor:
+        """Late-interaction scores of the queries against a resident index (``runtime.maxsim_index.TokenIndex``,
+        a rank's slice), fp32 on the engine's device. Without ``candidates``: ``[Q, index.count]``, every query
+        against every passage of the slice, one all-form launch. With ``candidates`` (one list of passage ids
+        of the file per query): ``[Q, C]``, ``C`` the longest list, entry ``[q, j]`` the score of
+        ``candidates[q][j]`` when that passage is in the slice and ``-inf`` when it is not (or past the list's
+        end): one list-form launch. ``self.maxsim_lens_q`` as in :meth:`maxsim_scores`."""
+        Q, P, dev = len(queries), self.late_dim, self.device
+        self._check_late(Q)
+        if int(index.tokens.shape[1]) != P:
+            raise ValueError("index width is not the model's token-vector width")
+        if candidates is not None and len(candidates) != Q:
+            raise ValueError("candidates must be one list per query")
+        qv, lens_q = self._maxsim_queries(queries)
+        if candidates is None:
+            if Q == 0 or index.count == 0:
+                return torch.empty((Q, index.count), dtype=torch.float32, device=dev)
+            return ops.maxsim_index(qv, lens_q, index.tokens, index.offsets)
+        out = torch.full((Q, max([len(c) for c in candidates], default=0)), float("-inf"), dtype=torch.float32, device=dev)
+        if Q == 0 or index.count == 0 or out.numel() == 0:
+            return out
+        pidx, qoff, qsel, col = self._candidate_entries(candidates, index)
+        if qsel.numel():
+            sc = ops.maxsim_index(qv, lens_q, index.tokens, index.offsets, pidx, qoff, qsel)
+            out[qsel.to(torch.int64), col] = sc
+        return out
+
+    def maxsim_index_rank(self, queries: Sequence, index, candidates: Optional[Sequence[Sequence[int]]] = None,
+                          top_k: int = 10) -> RerankResult:
+        """:meth:`maxsim_index_scores`, then :meth:`rank_scores` (one ``group_topk`` launch, one copy back).
+        Without ``candidates`` ``idx`` is the passage's position in the slice; with them its position in the
+        query's candidate list (only the list's own entries are ranked; one outside the slice scores ``-inf``)."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= ops.rerank.MAX_K:
+            raise ValueError("top_k must be an int in [1, 32]")
+        scores = self.maxsim_index_scores(queries, index, candidates)
+        Q, C = scores.shape
+        if candidates is None or all(len(c) == C for c in candidates):
+            return self.rank_scores(scores.reshape(-1), [q * C for q in range(Q + 1)], top_k)
+        goff = [0]
+        for c in candidates:
+            goff.append(goff[-1] + len(c))
+        flat = torch.cat([scores[q, :len(c)] for q, c in enumerate(candidates)])
+        return self.rank_scores(flat, goff, top_k)
 
     # ------------------------------------------------------ zero-shot classification (map_zero_shot)
     # An NLI model reads every text with one hypothesis per candidate label as ``[CLS] text [SEP]
