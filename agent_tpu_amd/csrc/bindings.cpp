@@ -331,6 +331,33 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("q"), py::arg("vectors"), py::arg("row_ids"), py::arg("offsets"), py::arg("item_cluster"),
       py::arg("item_query"), py::arg("item_slot"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"),
       py::arg("k"), py::arg("K"), py::arg("nprobe"), py::arg("S"), py::arg("items"), py::arg("stream"));
+  m.def("pq_shape_ok", &pq_shape_ok, "shapes the product-quantization kernels take", py::arg("D"), py::arg("M"));
+  m.def(
+      "pq_encode",
+      [](uintptr_t x, uintptr_t codebooks, uintptr_t bias, uintptr_t codes, int64_t n, int D, int M, uintptr_t stream) {
+        pq_encode(P<const float>(x), P<const float>(codebooks), P<const float>(bias), P<uint8_t>(codes), n, D, M,
+                  S(stream));
+      },
+      "PQ codes [n, M] uint8: per (row, sub-space) the arg-max codeword of dot + bias, ties to the lower id",
+      py::arg("x"), py::arg("codebooks"), py::arg("bias"), py::arg("codes"), py::arg("n"), py::arg("D"), py::arg("M"),
+      py::arg("stream"));
+  m.def(
+      "pq_lut",
+      [](uintptr_t q, uintptr_t codebooks, uintptr_t lut, int nq, int D, int M, uintptr_t stream) {
+        pq_lut(P<const float>(q), P<const float>(codebooks), P<float>(lut), nq, D, M, S(stream));
+      },
+      "ADC tables lut [nq, M, 256]: every query sub-vector against every codeword", py::arg("q"), py::arg("codebooks"),
+      py::arg("lut"), py::arg("nq"), py::arg("D"), py::arg("M"), py::arg("stream"));
+  m.def("pq_scan_splits", &pq_scan_splits, "the split count pq_scan_partial runs for a wanted one (no empty split)",
+        py::arg("N"), py::arg("want"));
+  m.def(
+      "pq_scan_partial",
+      [](uintptr_t lut, uintptr_t codes, uintptr_t ws, int nq, int N, int M, int k, int splits, uintptr_t stream) {
+        pq_scan_partial(P<const float>(lut), P<const uint8_t>(codes), P<float>(ws), nq, N, M, k, splits, S(stream));
+      },
+      "ADC scan of interleaved PQ codes with the top-k in the epilogue: every split's sorted top-k to ws [nq, P, k, 2]",
+      py::arg("lut"), py::arg("codes"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("M"), py::arg("k"),
+      py::arg("P"), py::arg("stream"));
   m.def("kmeans_shape_ok", &kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
   m.def(
       "kmeans_assign",

@@ -199,6 +199,27 @@ void sim_topk_ivf_partial(const float* q, const float* vectors, const int32_t* r
                           const int32_t* item_cluster, const int32_t* item_query, const int32_t* item_slot, float* ws,
                           int nq, int N, int D, int k, int K, int nprobe, int S, int items, hipStream_t stream);
 
+// ---------------------------------------------------------------- product quantization (pq.hip)
+// A row of D floats as M bytes: byte m = the codeword (of 256) of sub-space m, columns m * dsub .. + dsub - 1.
+// dsub = D / M in {4, 8, 16}, M a multiple of 4 in [4, kPqMaxSubvectors]. A sub-space dot product is the chain
+// p_0, + p_1, ... of separately rounded products (no FMA), in all three kernels.
+// pq_encode: codes[i, m] = arg-max over j of dot(x[i, sub m], codebooks[m, j]) + bias[m, j] (one fp32 add), ties
+// to the lower j (+0.0 and -0.0 tie); x [n, D], codebooks [M, 256, dsub], bias [M, 256], codes [n, M] row-major.
+// pq_lut: lut[i, m, j] = dot(q[i, sub m], codebooks[m, j]); lut [nq, M, 256].
+// pq_scan_partial: score(i, r) = lut[i, 0, code(r, 0)] + lut[i, 1, code(r, 1)] + ... in ascending m, one fp32
+// chain; every split's sorted top-k (value, row as int bits) goes to ws [nq, P, k, 2] for sim_topk_merge,
+// P = pq_scan_splits(N, wanted) <= kSimMaxSplits (no empty split). codes is the interleaved layout
+// [ceil(N / 64)][M / 4][64][4] bytes: byte e of dword (b, m4, lane) = code(64 b + lane, 4 m4 + e), the rows past N
+// of the last block present (any value). k in [1, 32], N < 2^31 - 256. Nothing outside these tensors is read.
+constexpr int kPqMaxSubvectors = 128;
+bool pq_shape_ok(int D, int M);
+void pq_encode(const float* x, const float* codebooks, const float* bias, uint8_t* codes, int64_t n, int D, int M,
+               hipStream_t stream);
+void pq_lut(const float* q, const float* codebooks, float* lut, int nq, int D, int M, hipStream_t stream);
+int pq_scan_splits(int N, int want);
+void pq_scan_partial(const float* lut, const uint8_t* codes, float* ws, int nq, int N, int M, int k, int P,
+                     hipStream_t stream);
+
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)
 // in the order of better() (score desc, centroid asc), best[i] that score; every score is one fp32

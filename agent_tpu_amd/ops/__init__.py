@@ -23,6 +23,10 @@ from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
 from .search import (RowMask, row_mask_from_ids, row_mask_from_ids_ref, row_mask_from_labels,  # noqa: F401
                      row_mask_from_labels_ref, row_mask_from_bits, row_mask_bits)
 from .search import sim_topk_ivf, sim_topk_ivf_ref, ivf_labels, ivf_plan  # noqa: F401
+from .pq import (pq_ok, pq_encode, pq_encode_ref, pq_lut, pq_lut_ref, pq_scan_topk, pq_scan_topk_ref,  # noqa: F401
+                 sim_topk_pq, sim_topk_pq_ref, pq_bias, pq_interleave, pq_deinterleave, PqCodes)
+from .pq import decode as pq_decode  # noqa: F401  (ops.decode stays the decode-attention module)
+from .cluster import to_fixed  # noqa: F401
 from .cluster import (kmeans_assign, kmeans_assign_ref, kmeans_update, kmeans_update_ref, kmeans_finalize,  # noqa: F401
                       kmeans_finalize_ref, fixed_shift, fixed_sum, fixed_sum_ref, kmeans_ok)
 from .dedup import (sim_join, sim_join_ok, sim_join_ref, sort_pairs, cc_min_labels,  # noqa: F401

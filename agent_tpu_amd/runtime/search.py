@@ -12,7 +12,8 @@ rounded to nearest) at half the bytes, and cosine keeps the rows unnormalised be
 ``row_scale = 1 / max(||row||_2, 1e-12)`` that ``sim_topk`` multiplies into the finished score.
 
 The IVF indexes of ``runtime/ivf.py`` are entries of the same LRU, under the corpus key extended by
-``("ivf", clusters, train_iterations)``.
+``("ivf", clusters, train_iterations)``, and the product-quantized corpora of ``runtime/pq.py`` under
+``("pq", subvectors, train_rows, train_iterations, normalised?)``.
 """
 from __future__ import annotations
 

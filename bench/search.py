@@ -22,6 +22,11 @@ gather routes, alternating; one JSON line per (N, queries, density, variant, rou
 ``--ivf-clusters K`` with ``--nprobe n [n ...]`` measures the IVF index instead (:func:`ivf_bench`): the
 exact search and ``ops.sim_topk_ivf`` on the same tensors, alternating, with recall against the exact result,
 the build time and the probe-and-plan time; one JSON line per (N, queries, nprobe, variant, round).
+
+``--pq-subvectors M`` measures the product-quantized search instead (:func:`pq_bench`): the exact fp16-resident
+search and ``ops.sim_topk_pq`` over ``M``-byte codes of the same rows, alternating, with the resident bytes of
+both, recall against the exact result and the training and encoding times; one JSON line per (N, queries, variant,
+round).
 """
 from __future__ import annotations
 
@@ -184,6 +189,94 @@ def ivf_bench(a, ops, dev) -> int:
     return 0
 
 
+def pq_bench(a, ops, dev) -> int:
+    """``--pq-subvectors M``: the product-quantized search against the exact fp16-resident one on the same rows.
+    The corpus is :func:`ivf_bench`'s seeded Gaussian mixture (``--ivf-clusters`` centres, default 1024 here;
+    ``--ivf-noise``): the recall figures say how PQ does on clustered synthetic data, not on a text corpus. The
+    codebooks are trained by ``runtime.pq.train`` on the seeded sample of ``--pq-train-rows`` rows and the corpus is
+    encoded in chunks (both timed once, host clock around a synchronise). Per (N, queries) three arms alternate for
+    ``--rounds`` rounds: ``exact_f16`` (``ops.sim_topk`` over the rows as fp16), ``pq`` (``ops.sim_topk_pq``: the
+    table kernel, the scan and the merge) and ``pq_lut`` (the table kernel alone); ``--query-sets`` query batches
+    rotate in every arm. ``recall`` is the mean share of the exact fp16 top-k that the PQ list holds,
+    ``resident_bytes`` what each arm keeps on the device."""
+    import time
+
+    from agent_tpu_amd.runtime import pq
+    from agent_tpu_amd.runtime.search import CHUNK_BYTES, normalize_rows
+
+    D, k, M = a.dim, a.top_k, a.pq_subvectors
+    K = a.ivf_clusters or 1024
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def mixture(n, centres):
+        pick = torch.randint(0, centres.shape[0], (n,), device=dev, generator=gen)
+        return normalize_rows(centres[pick] + a.ivf_noise * torch.randn(n, D, device=dev, generator=gen)).contiguous()
+
+    for N in a.rows:
+        centres = normalize_rows(torch.randn(K, D, device=dev, generator=gen))
+        x = mixture(N, centres)
+        T = min(N, a.pq_train_rows)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        books = pq.train(x[pq.sample_rows(N, T).to(dev)].contiguous(), M, a.pq_train_iterations)
+        torch.cuda.synchronize(dev)
+        train_ms = (time.perf_counter() - t0) * 1e3
+        bias = ops.pq_bias(books)
+        rows = max(64, CHUNK_BYTES // (D * 4) // 64 * 64)
+        t0 = time.perf_counter()
+        codes = ops.pq_interleave(torch.cat([ops.pq_encode(x[lo:lo + rows], books, bias) for lo in range(0, N, rows)]))
+        torch.cuda.synchronize(dev)
+        encode_ms = (time.perf_counter() - t0) * 1e3
+        err = float((x[:65536] - ops.pq_decode(ops.pq_deinterleave(codes)[:65536], books)).norm(dim=1).mean())
+        x16 = x.half()
+        del x
+        resident = {"exact_f16": x16.numel() * 2, "pq": codes.data.numel() + books.numel() * 4, "pq_lut": 0}
+        for nq in a.queries:
+            qs = [mixture(nq, centres) for _ in range(a.query_sets)]
+
+            def exact(i):
+                return ops.sim_topk(qs[i], x16, k, splits=a.splits or None)
+
+            def approx(i):
+                return ops.sim_topk_pq(qs[i], books, codes, k, splits=a.splits or None)
+
+            def lut(i):
+                return ops.pq_lut(qs[i], books)
+
+            def timed(fn):
+                for i in range(a.query_sets):
+                    fn(i)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for it in range(a.iters):
+                    fn(it % a.query_sets)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
+
+            hit = top1 = 0
+            for i in range(a.query_sets):
+                ei, ai = exact(i)[1], approx(i)[1]
+                hit += int((ai[:, :, None] == ei[:, None, :]).any(1).sum())
+                top1 += int((ai[:, 0] == ei[:, 0]).sum())
+            recall = hit / (a.query_sets * nq * k)
+            for r in range(a.rounds):
+                for variant, fn in (("exact_f16", exact), ("pq", approx), ("pq_lut", lut)):
+                    us = timed(fn)
+                    print(json.dumps({"bench": "search_pq", "variant": variant, "N": N, "queries": nq, "dim": D,
+                                      "top_k": k, "subvectors": M, "bytes_per_row": M, "round": r,
+                                      "us_per_call": round(us, 2), "resident_bytes": resident[variant],
+                                      "recall": round(recall, 4), "top1_agreement": round(top1 / (a.query_sets * nq), 4),
+                                      "train_ms": round(train_ms, 1), "encode_ms": round(encode_ms, 1),
+                                      "train_rows": T, "train_iterations": a.pq_train_iterations,
+                                      "mean_reconstruction_error": round(err, 4), "mixture_centres": K,
+                                      "noise": a.ivf_noise, "query_sets": a.query_sets,
+                                      "splits": a.splits or ops.pq.pq_auto_splits(N, dev)}), flush=True)
+        del x16, codes
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
@@ -203,6 +296,10 @@ def main() -> int:
     ap.add_argument("--ivf-train-iterations", type=int, default=10)
     ap.add_argument("--ivf-noise", type=float, default=0.05, help="per-column noise of the IVF mixture corpus")
     ap.add_argument("--query-sets", type=int, default=16, help="query batches that the IVF comparison rotates through")
+    ap.add_argument("--pq-subvectors", type=int, default=0,
+                    help="run the product-quantization comparison with this many bytes per row instead")
+    ap.add_argument("--pq-train-rows", type=int, default=65536)
+    ap.add_argument("--pq-train-iterations", type=int, default=10)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -212,6 +309,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     if a.filter_density:
         return filter_bench(a, ops, dev)
+    if a.pq_subvectors:
+        return pq_bench(a, ops, dev)
     if a.ivf_clusters:
         return ivf_bench(a, ops, dev)
     D, k = a.dim, a.top_k

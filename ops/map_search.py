@@ -10,6 +10,9 @@ or a range: the rows become a bit mask on the device and the kernel applies it i
 ``index`` asks for an approximate search through an inverted-file (IVF) index: the resident corpus sorted by
 k-means cluster (``agent_tpu_amd/runtime/ivf.py``), every query scored against the rows of the ``nprobe``
 clusters nearest to it only (``ops.sim_topk_ivf``); the scores stay exact and the ids are the original rows.
+``compression`` keeps the corpus product-quantized (``agent_tpu_amd/runtime/pq.py``): ``subvectors`` bytes per row
+instead of ``4 dim``, scored from a per-query table of sub-vector dot products (``ops.sim_topk_pq``); the scores
+are approximate.
 
 Under ``torchrun`` every rank embeds the queries, searches its slice of the corpus, and rank 0
 merges the per-rank lists in the same total order (score descending, id ascending). Errors are
@@ -78,6 +81,22 @@ INDEX_KEYS = ("type", "clusters", "nprobe", "train_iterations")
 MAX_CLUSTERS = 4096
 MAX_NPROBE = 32  # sim_topk's MAX_K: the probe is a sim_topk call
 MAX_TRAIN_ITERATIONS = 100
+#: those of ``compression`` (also in the contract)
+PQ_ERRORS: Dict[str, str] = {
+    "compression": ("payload.compression must be {'type': 'pq', 'subvectors': M} with an integer M, a multiple of 4 up to "
+                    "128 with corpus dim / M of 4, 8 or 16, and optional integers 'train_rows' in "
+                    "[256, min(corpus rows, 1048576)] and 'train_iterations' in [1, 100]"),
+    "compression_corpus": "payload.compression needs payload.corpus_uri (a resident corpus)",
+    "compression_rows": "payload.compression needs a corpus of at least 256 rows",
+    "compression_filter": "payload.compression cannot be combined with payload.filter",
+    "compression_index": "payload.compression cannot be combined with payload.index",
+    "compression_f16": "payload.compression cannot be combined with corpus_dtype 'float16' (the codes are the resident form)",
+    "compression_too_large": "compressed corpus slice exceeds SEARCH_INDEX_MAX_GB of codes",
+}
+COMPRESSION_KEYS = ("type", "subvectors", "train_rows", "train_iterations")
+MAX_SUBVECTORS = 128
+MIN_PQ_ROWS = 256
+MAX_PQ_TRAIN_ROWS = 1048576
 
 
 class Options(NamedTuple):
@@ -89,6 +108,7 @@ class Options(NamedTuple):
     filter: Optional[tuple] = None  # canonical: (key, sorted unique values or the (lo, hi) pair)
     labels_uri: Optional[str] = None  # corpus_labels_uri, kept only when a label filter uses it
     index: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, train_iterations)
+    compression: Optional[tuple] = None  # canonical: (subvectors, train_rows or None, train_iterations)
 
 
 def _number(x: Any) -> bool:
@@ -174,6 +194,54 @@ def resolve_index(index: tuple, total: int) -> tuple:
     return clusters, nprobe, t
 
 
+def parse_compression(payload: Dict[str, Any]) -> tuple:
+    """``payload.compression`` in canonical form, ``(subvectors, train_rows or None, train_iterations)``: everything
+    about it that can be refused without the corpus (:func:`resolve_compression` does the rest)."""
+    cp = payload["compression"]
+    if not isinstance(cp, dict) or cp.get("type") != "pq" or not set(cp) <= set(COMPRESSION_KEYS):
+        raise ValueError(PQ_ERRORS["compression"])
+
+    def integer(key, lo, hi, default):
+        if key not in cp:
+            return default
+        v = cp[key]
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError(PQ_ERRORS["compression"])
+        return v
+
+    canon = (integer("subvectors", 4, MAX_SUBVECTORS, None), integer("train_rows", MIN_PQ_ROWS, MAX_PQ_TRAIN_ROWS, None),
+             integer("train_iterations", 1, MAX_TRAIN_ITERATIONS, 10))
+    if canon[0] is None or canon[0] % 4:
+        raise ValueError(PQ_ERRORS["compression"])
+    if "corpus_uri" not in payload:
+        raise ValueError(PQ_ERRORS["compression_corpus"])
+    if payload.get("corpus_dtype") == "float16":  # an explicit one; the environment's default does not apply to codes
+        raise ValueError(PQ_ERRORS["compression_f16"])
+    if "filter" in payload:
+        raise ValueError(PQ_ERRORS["compression_filter"])
+    if "index" in payload:
+        raise ValueError(PQ_ERRORS["compression_index"])
+    return canon
+
+
+def resolve_compression(compression: tuple, total: int, dim: int) -> tuple:
+    """(subvectors, train_rows, train_iterations) of a canonical ``compression`` for a corpus of ``total`` rows of
+    ``dim`` columns: the default ``train_rows = min(total, 65536)`` and the bounds that need the corpus."""
+    from agent_tpu_amd.ops import pq_ok
+    from agent_tpu_amd.runtime.pq import default_train_rows
+
+    M, T, t = compression
+    if total < MIN_PQ_ROWS:
+        raise ValueError(PQ_ERRORS["compression_rows"])
+    if not pq_ok(dim, M):
+        raise ValueError(PQ_ERRORS["compression"])
+    if T is None:
+        T = default_train_rows(total)
+    elif T > total:
+        raise ValueError(PQ_ERRORS["compression"])
+    return M, T, t
+
+
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work."""
     top_k = payload.get("top_k", 10)
@@ -228,6 +296,8 @@ def check_payload(payload: Dict[str, Any]) -> Options:
         opt = opt._replace(filter=flt, labels_uri=labels_uri)
     if "index" in payload:  # likewise: a job without one is untouched
         opt = opt._replace(index=parse_index(payload, opt))
+    if "compression" in payload:  # likewise
+        opt = opt._replace(compression=parse_compression(payload))
     return opt
 
 
@@ -372,6 +442,53 @@ def search_queries_ivf(device, qvecs, payload: Dict[str, Any], top_k: int, index
     return s, i, total, idx.cached, info
 
 
+def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, compression: tuple, rank: int,
+                      ws: int):
+    """:func:`search_queries` over a product-quantized corpus (``runtime/pq.py``): every rank trains the same
+    codebooks from the same sample of the file (no collective), encodes its own slice chunk by chunk and scans its
+    codes with ``id_base`` = the slice start; the lists are padded to ``top_k``, all-gathered and merged as the exact
+    ones are. A row's ADC score depends on the query, the codebooks and the row's codes only, so the result has the
+    same bits for every world size. -> (scores, ids on the host; corpus rows; index_cached; the result's
+    ``compression`` dict) on rank 0, None elsewhere."""
+    import torch
+
+    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
+    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
+    from agent_tpu_amd.runtime import pq
+    from agent_tpu_amd.runtime import search as rs
+
+    exc, s, i, total, cached, info = None, None, None, 0, None, None
+    nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
+    try:
+        total, cdim = rs.corpus_shape(payload["corpus_uri"])
+        if cdim != dim:
+            raise ValueError(ERRORS["dim"])
+        M, T, t = resolve_compression(compression, total, cdim)
+        s_r, n_r = split_range(0, total, ws, rank)
+        idx = pq.load_index(payload["corpus_uri"], s_r, n_r, device, M, T, t, metric == "cosine")
+        cached = idx.cached
+        info = {"type": "pq", "subvectors": M, "train_rows": T, "train_iterations": t, "bytes_per_row": M}
+        maybe_inject_fault("search")
+        s, i = pq.search(qvecs, idx, top_k, id_base=s_r)
+        if s.shape[1] < top_k:  # a slice shorter than top_k: pad, so every rank gathers [nq, top_k]
+            pad = top_k - s.shape[1]
+            s = torch.cat([s, torch.full((nq, pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
+            i = torch.cat([i, torch.full((nq, pad), PAD_ID, dtype=i.dtype, device=i.device)], 1)
+    except Exception as e:
+        exc = e
+    counts = exchange_errors(exc, nq if s is not None else 0)
+    s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
+    if rank != 0:
+        return None
+    s, i = s.cpu(), i.cpu()
+    if ws > 1:  # as search_queries: every query's ws lists side by side -> merged; the padding sorts last
+        s = s.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        s, i = rs.merge_topk(s, i, top_k)
+    kk = min(top_k, total)
+    return s[:, :kk], i[:, :kk], total, cached, info
+
+
 def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str]], metric: str, pooling: str):
     """``[nq, dim]`` fp32 query vectors: the model's embeddings of ``queries``, or ``query_vectors``
     on the device (normalised there for cosine)."""
@@ -387,7 +504,8 @@ def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str
 
 
 def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim: int, cached: Optional[bool],
-           ws: int, filter_rows: Optional[int] = None, index_info: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+           ws: int, filter_rows: Optional[int] = None, index_info: Optional[Dict[str, Any]] = None,
+           compression_info: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
     """One job's result from its rows of the merged lists (rank 0): the first ``top_k`` entries (with
     a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host.
     ``filter_rows``: the corpus rows that passed the job's filter (None: no filter). ``index_info``: the
@@ -414,12 +532,15 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         out["dp_world_size"] = ws
     if cached is not None:
         out["index_cached"] = bool(cached)
-    if "corpus_uri" in payload and opt.corpus_dtype != "float32":  # default-path results keep their keys
+    # default-path results keep their keys; a compressed corpus is resident as codes, whatever the default dtype
+    if "corpus_uri" in payload and opt.corpus_dtype != "float32" and compression_info is None:
         out["corpus_dtype"] = opt.corpus_dtype
     if filter_rows is not None:
         out["filter_rows"] = int(filter_rows)
     if index_info is not None:
         out["index"] = dict(index_info)
+    if compression_info is not None:
+        out["compression"] = dict(compression_info)
     out.update(ids=ids_l, scores=sc_l)
     return out
 
@@ -456,6 +577,12 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
             return None
         s, i, total, cached, info = got
         return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, index_info=info)
+    if opt.compression is not None:  # likewise
+        got = search_queries_pq(device, qv, payload, opt.top_k, opt.metric, opt.compression, rank, ws)
+        if got is None:
+            return None
+        s, i, total, cached, info = got
+        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info)
     got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
                          opt.filter, opt.labels_uri)
     if got is None:
@@ -466,8 +593,8 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
 
 def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional[List[Any]]:
     """The ``queries`` + ``corpus_uri`` jobs of one lease that share (model, pooling, metric, corpus,
-    corpus_dtype, canonical filter and its label file) as one engine call (every rank calls it): one
-    embed of the concatenated queries, one search at the
+    corpus_dtype, canonical filter and its label file, canonical index, canonical compression) as one engine
+    call (every rank calls it): one embed of the concatenated queries, one search at the
     group's largest ``top_k``; each job takes the first ``top_k`` entries of its own rows."""
     out: List[Any] = [None] * len(payloads)
     jobs = []
@@ -493,21 +620,24 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 qv = torch.cat([h.engine.embed_texts(ts, key.pooling, key.metric == "cosine").emb for _, _, ts in jobs])
             if key.index is not None:  # the group shares the canonical index, nprobe included
                 got = search_queries_ivf(device, qv, first, K, key.index, rank, ws)
-                got = None if got is None else got[:4] + (None, got[4])
+                got = None if got is None else got[:4] + (None, got[4], None)
+            elif key.compression is not None:  # the group shares the canonical compression
+                got = search_queries_pq(device, qv, first, K, key.metric, key.compression, rank, ws)
+                got = None if got is None else got[:4] + (None, None, got[4])
             else:
                 got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
                                      key.filter, key.labels_uri)
-                got = None if got is None else got + (None,)
+                got = None if got is None else got + (None, None)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
                 out[n] = ("err", exc)
             return out if rank == 0 else None
         if got is not None:
-            s, i, total, cached, filter_rows, info = got
+            s, i, total, cached, filter_rows, info, cinfo = got
             pos = 0
             for n, opt, ts in jobs:
                 out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
-                                       int(qv.shape[1]), cached, ws, filter_rows, info))
+                                       int(qv.shape[1]), cached, ws, filter_rows, info, cinfo))
                 pos += len(ts)
     return out if rank == 0 else None
 
@@ -516,7 +646,8 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``queries`` + ``corpus_uri`` jobs that share (model_path, pooling, metric,
     corpus_uri, corpus_dtype, with a ``filter`` its canonical form and label file, and with an ``index`` its
-    canonical (clusters, train_iterations) and nprobe) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
+    canonical (clusters, train_iterations) and nprobe, and with a ``compression`` its canonical tuple) go to the device
+    together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
     single-job path."""
 
     def key(p):
@@ -527,6 +658,8 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
         if opt.index is not None:  # (clusters, train_iterations) name the index; jobs that differ in nprobe probe
             clusters, nprobe, t = opt.index  # other rows per query, so they stay separate groups
             return group + ("ivf", clusters, t, nprobe)
+        if opt.compression is not None:  # the canonical tuple names the codebooks and the codes
+            return group + ("pq",) + opt.compression
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
     return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
