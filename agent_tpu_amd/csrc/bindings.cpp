@@ -358,6 +358,38 @@ PYBIND11_MODULE(_atpu, m) {
       "ADC scan of interleaved PQ codes with the top-k in the epilogue: every split's sorted top-k to ws [nq, P, k, 2]",
       py::arg("lut"), py::arg("codes"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("M"), py::arg("k"),
       py::arg("P"), py::arg("stream"));
+  m.def(
+      "pq_encode_residual",
+      [](uintptr_t x, uintptr_t labels, uintptr_t centroids, uintptr_t codebooks, uintptr_t bias, uintptr_t codes,
+         int64_t n, int D, int M, int K, uintptr_t stream) {
+        pq_encode_residual(P<const float>(x), P<const int32_t>(labels), P<const float>(centroids),
+                           P<const float>(codebooks), P<const float>(bias), P<uint8_t>(codes), n, D, M, K, S(stream));
+      },
+      "PQ codes [n, M] uint8 of the residuals x - centroids[labels], subtracted in registers",
+      py::arg("x"), py::arg("labels"), py::arg("centroids"), py::arg("codebooks"), py::arg("bias"), py::arg("codes"),
+      py::arg("n"), py::arg("D"), py::arg("M"), py::arg("K"), py::arg("stream"));
+  m.def(
+      "pq_coarse",
+      [](uintptr_t q, uintptr_t centroids, uintptr_t probes, uintptr_t coarse, int nq, int D, int K, int nprobe,
+         uintptr_t stream) {
+        pq_coarse(P<const float>(q), P<const float>(centroids), P<const int64_t>(probes), P<float>(coarse), nq, D, K,
+                  nprobe, S(stream));
+      },
+      "coarse [nq, nprobe]: dot(q, centroids[probes]) in a fixed fp32 order", py::arg("q"), py::arg("centroids"),
+      py::arg("probes"), py::arg("coarse"), py::arg("nq"), py::arg("D"), py::arg("K"), py::arg("nprobe"),
+      py::arg("stream"));
+  m.def(
+      "pq_scan_ivf_partial",
+      [](uintptr_t lut, uintptr_t codes, uintptr_t row_ids, uintptr_t offsets, uintptr_t probes, uintptr_t coarse,
+         uintptr_t ws, int nq, int N, int M, int k, int K, int nprobe, int splits, uintptr_t stream) {
+        pq_scan_ivf_partial(P<const float>(lut), P<const uint8_t>(codes), P<const int32_t>(row_ids),
+                            P<const int32_t>(offsets), P<const int64_t>(probes), P<const float>(coarse), P<float>(ws), nq,
+                            N, M, k, K, nprobe, splits, S(stream));
+      },
+      "query-stationary ADC scan of the probed clusters' residual codes: (query, split) top-k to ws [nq, S, k, 2]",
+      py::arg("lut"), py::arg("codes"), py::arg("row_ids"), py::arg("offsets"), py::arg("probes"), py::arg("coarse"),
+      py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("M"), py::arg("k"), py::arg("K"), py::arg("nprobe"),
+      py::arg("S"), py::arg("stream"));
   m.def("kmeans_shape_ok", &kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
   m.def(
       "kmeans_assign",

@@ -25,6 +25,9 @@ PKG = HERE.parent
 REPO = PKG.parent
 BUILD = REPO / "build" / "obj"
 ARCH = os.environ.get("ATPU_ARCH", "gfx950")
+#: translation units compiled without the packed fp32 VALU instructions (v_pk_add_f32 and its kin): their
+#: independent fp32 add chains are kept as scalar-per-lane adds
+NO_PACKED_FP32 = {"pq_ivf.hip"}
 
 
 def _hipcc() -> str:
@@ -66,6 +69,8 @@ def _compile(src: Path, flags: List[str], force: bool) -> Path:
     obj = BUILD / (src.parent.name + "__" + src.stem + ".o")
     if not force and obj.exists() and obj.stat().st_mtime >= max(src.stat().st_mtime, _header_mtime()):
         return obj
+    if src.name in NO_PACKED_FP32:
+        flags = flags + ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     cmd = [_hipcc(), *flags, "-c", str(src), "-o", str(obj)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:

@@ -219,6 +219,24 @@ void pq_lut(const float* q, const float* codebooks, float* lut, int nq, int D, i
 int pq_scan_splits(int N, int want);
 void pq_scan_partial(const float* lut, const uint8_t* codes, float* ws, int nq, int N, int M, int k, int P,
                      hipStream_t stream);
+// IVF-PQ (pq_ivf.hip): PQ codes of the residual x - centroids[label] over rows sorted by cluster (row_ids [N] int32:
+// the original row of a sorted row; offsets [K + 1] int32), one interleaved image over the sorted rows.
+// pq_encode_residual: pq_encode of x[i] - centroids[labels[i]] (an fp32 subtract, in registers); labels [n] int32
+// (clamped into [0, K)), centroids [K, D].
+// pq_coarse: coarse[i, s] = dot(q[i], centroids[probes[i, s]]) in a fixed order that depends on D alone (16 strided
+// chains of separately rounded products and a butterfly of adds); probes [nq, nprobe] int64, D % 64 == 0.
+// pq_scan_ivf_partial: query i scans the rows of the clusters probes[i, :] (an id outside [0, K): an empty cluster);
+// score = (lut[i, 0, code_0] + ... + lut[i, M-1, code_{M-1}]) + coarse[i, slot]. Grid (nq, S): the sorted top-k
+// (value, ORIGINAL row as int bits) of (query, split) goes to ws [nq, S, k, 2], every slot written, for
+// sim_topk_merge with P = S <= kSimMaxSplits. K in [1, 4096], nprobe in [1, min(32, K)]. Nothing outside these
+// tensors is read.
+void pq_encode_residual(const float* x, const int32_t* labels, const float* centroids, const float* codebooks,
+                        const float* bias, uint8_t* codes, int64_t n, int D, int M, int K, hipStream_t stream);
+void pq_coarse(const float* q, const float* centroids, const int64_t* probes, float* coarse, int nq, int D, int K,
+               int nprobe, hipStream_t stream);
+void pq_scan_ivf_partial(const float* lut, const uint8_t* codes, const int32_t* row_ids, const int32_t* offsets,
+                         const int64_t* probes, const float* coarse, float* ws, int nq, int N, int M, int k, int K,
+                         int nprobe, int S, hipStream_t stream);
 
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)

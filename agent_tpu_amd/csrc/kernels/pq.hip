@@ -33,37 +33,13 @@
 // their scores are discarded by select. Nothing outside lut, the blocks [0, ceil(N / 64)) and ws is touched.
 #include "atpu/common.h"
 #include "atpu/kernels.h"
+#include "atpu/pq.h"
 #include "atpu/topk.h"
 
 namespace atpu {
 namespace {
 
-constexpr int kPqCodewords = 256;
-constexpr int kPqThreads = 256;  // encode and table kernels
-constexpr int kPqScanWaves = 8;
-constexpr int kPqScanThreads = kPqScanWaves * kWave;
-constexpr int kPqBlock = 64;   // rows of one interleaved block: one per lane
-constexpr int kPqChains = 4;   // blocks (rows per lane) of one wave step
 constexpr int kNoRow = 0x7fffffff;
-
-template <int DSUB>
-__device__ __forceinline__ float pq_dot(const float (&x)[DSUB], const float* __restrict__ c) {
-  // Plain operators under the pragma, not __fmul_rn / __fadd_rn: those are header functions compiled under the
-  // default contraction mode, and once inlined their multiply and add were fused into v_fmac_f32.
-#pragma clang fp contract(off)
-  float acc = x[0] * c[0];
-#pragma unroll
-  for (int d = 1; d < DSUB; ++d) {
-    const float p = x[d] * c[d];
-    acc = acc + p;
-  }
-  return acc;
-}
-
-__device__ __forceinline__ float pq_add(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
 
 template <int DSUB>
 __global__ __launch_bounds__(kPqThreads) void pq_encode_kernel(const float* __restrict__ x,

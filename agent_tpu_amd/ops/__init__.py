@@ -26,6 +26,8 @@ from .search import sim_topk_ivf, sim_topk_ivf_ref, ivf_labels, ivf_plan  # noqa
 from .pq import (pq_ok, pq_encode, pq_encode_ref, pq_lut, pq_lut_ref, pq_scan_topk, pq_scan_topk_ref,  # noqa: F401
                  sim_topk_pq, sim_topk_pq_ref, pq_bias, pq_interleave, pq_deinterleave, PqCodes)
 from .pq import decode as pq_decode  # noqa: F401  (ops.decode stays the decode-attention module)
+from .pq_ivf import (pq_encode_residual, pq_encode_residual_ref, pq_coarse, pq_coarse_ref,  # noqa: F401
+                     sim_topk_ivfpq, sim_topk_ivfpq_ref)
 from .cluster import to_fixed  # noqa: F401
 from .cluster import (kmeans_assign, kmeans_assign_ref, kmeans_update, kmeans_update_ref, kmeans_finalize,  # noqa: F401
                       kmeans_finalize_ref, fixed_shift, fixed_sum, fixed_sum_ref, kmeans_ok)

@@ -277,6 +277,74 @@ def pq_bench(a, ops, dev) -> int:
     return 0
 
 
+def ivfpq_bench(a, ops, dev) -> int:
+    """``--ivfpq-clusters K`` (with ``--pq-subvectors M``): flat PQ, IVF fp32 and IVF-PQ on the same seeded mixture
+    corpus (``K`` centres, ``--ivf-noise``), ``M`` and ``--nprobe`` values. The three indexes are built from in-memory
+    tensors with the runtime's own pieces (``runtime.pq.train``, ``runtime.ivf.build``, ``runtime.ivfpq.train`` and the
+    residual encoder). Per (N, queries, nprobe) the arms alternate for ``--rounds`` rounds; ``recall`` is the mean
+    share of the exact fp32 top-k (``ops.sim_topk``) that the arm's list holds, ``queries_per_sec`` counts whole
+    calls: probe, tables, scan and merge."""
+    from agent_tpu_amd.runtime import ivf, ivfpq, pq
+    from agent_tpu_amd.runtime.search import CHUNK_BYTES, normalize_rows
+
+    D, k, M, K = a.dim, a.top_k, a.pq_subvectors or 96, a.ivfpq_clusters
+    t = a.pq_train_iterations
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def mixture(n, centres):
+        pick = torch.randint(0, centres.shape[0], (n,), device=dev, generator=gen)
+        return normalize_rows(centres[pick] + a.ivf_noise * torch.randn(n, D, device=dev, generator=gen)).contiguous()
+
+    for N in a.rows:
+        centres = normalize_rows(torch.randn(K, D, device=dev, generator=gen))
+        x = mixture(N, centres)
+        sample = x[pq.sample_rows(N, min(N, a.pq_train_rows)).to(dev)].contiguous()
+        rows = max(64, CHUNK_BYTES // (D * 4) // 64 * 64)
+        books = pq.train(sample, M, t)
+        bias = ops.pq_bias(books)
+        flat = ops.pq_interleave(torch.cat([ops.pq_encode(x[lo:lo + rows], books, bias) for lo in range(0, N, rows)]))
+        cent, rbooks, _, _ = ivfpq.train(sample, K, M, t)
+        rbias = ops.pq_bias(rbooks)
+        labels = torch.cat([ops.kmeans_assign(x[lo:lo + rows], cent)[0] for lo in range(0, N, rows)])
+        rcodes = torch.cat([ops.pq_encode_residual(x[lo:lo + rows], labels[lo:lo + rows].contiguous(), cent, rbooks, rbias)
+                            for lo in range(0, N, rows)])
+        order = torch.sort(labels.long(), stable=True).indices
+        off = torch.zeros(K + 1, dtype=torch.int32, device=dev)
+        off[1:] = torch.cumsum(torch.bincount(labels.long(), minlength=K), 0).to(torch.int32)
+        rcodes, rid = ops.pq_interleave(rcodes[order].contiguous()), order.to(torch.int32).contiguous()
+        vec, vid, voff, vcent, _, _ = ivf.build(x, K, a.ivf_train_iterations)
+        resident = {"pq": flat.data.numel(), "ivf": vec.numel() * 4 + N * 4, "ivfpq": rcodes.data.numel() + N * 4}
+        for nq in a.queries:
+            qs = [mixture(nq, centres) for _ in range(a.query_sets)]
+            exact = [ops.sim_topk(q, x, k)[1] for q in qs]
+            for nprobe in a.nprobe:
+                arms = {"pq": lambda i: ops.sim_topk_pq(qs[i], books, flat, k)[1],
+                        "ivf": lambda i: ops.sim_topk_ivf(qs[i], vec, vid, voff, vcent, k, nprobe)[1],
+                        "ivfpq": lambda i: ops.sim_topk_ivfpq(qs[i], rbooks, rcodes, rid, off, cent, k, nprobe,
+                                                              splits=a.splits or None)[1]}
+                recall = {v: sum(int((fn(i)[:, :, None] == exact[i][:, None, :]).any(1).sum())
+                                 for i in range(a.query_sets)) / (a.query_sets * nq * k) for v, fn in arms.items()}
+                for r in range(a.rounds):
+                    for variant, fn in arms.items():
+                        for i in range(a.query_sets):
+                            fn(i)
+                        torch.cuda.synchronize(dev)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for it in range(a.iters):
+                            fn(it % a.query_sets)
+                        e1.record()
+                        torch.cuda.synchronize(dev)
+                        us = e0.elapsed_time(e1) * 1e3 / a.iters
+                        print(json.dumps({"bench": "search_ivfpq", "variant": variant, "N": N, "queries": nq, "dim": D,
+                                          "top_k": k, "subvectors": M, "clusters": K, "nprobe": nprobe, "round": r,
+                                          "us_per_call": round(us, 2), "queries_per_sec": round(nq * 1e6 / us, 1),
+                                          "recall": round(recall[variant], 4), "resident_bytes": resident[variant],
+                                          "noise": a.ivf_noise, "query_sets": a.query_sets}), flush=True)
+        del x, flat, rcodes, vec
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
@@ -298,6 +366,8 @@ def main() -> int:
     ap.add_argument("--query-sets", type=int, default=16, help="query batches that the IVF comparison rotates through")
     ap.add_argument("--pq-subvectors", type=int, default=0,
                     help="run the product-quantization comparison with this many bytes per row instead")
+    ap.add_argument("--ivfpq-clusters", type=int, default=0,
+                    help="compare flat PQ, IVF fp32 and IVF-PQ with this many clusters instead (M from --pq-subvectors)")
     ap.add_argument("--pq-train-rows", type=int, default=65536)
     ap.add_argument("--pq-train-iterations", type=int, default=10)
     a = ap.parse_args()
@@ -309,6 +379,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     if a.filter_density:
         return filter_bench(a, ops, dev)
+    if a.ivfpq_clusters:
+        return ivfpq_bench(a, ops, dev)
     if a.pq_subvectors:
         return pq_bench(a, ops, dev)
     if a.ivf_clusters:

@@ -10,6 +10,9 @@ or a range: the rows become a bit mask on the device and the kernel applies it i
 ``index`` asks for an approximate search through an inverted-file (IVF) index: the resident corpus sorted by
 k-means cluster (``agent_tpu_amd/runtime/ivf.py``), every query scored against the rows of the ``nprobe``
 clusters nearest to it only (``ops.sim_topk_ivf``); the scores stay exact and the ids are the original rows.
+``index`` of type ``ivfpq`` combines the two below (``agent_tpu_amd/runtime/ivfpq.py``): coarse clusters with
+product-quantization codes of the residuals, every query scored against the codes of the clusters it probes only
+(``ops.sim_topk_ivfpq``).
 ``compression`` keeps the corpus product-quantized (``agent_tpu_amd/runtime/pq.py``): ``subvectors`` bytes per row
 instead of ``4 dim``, scored from a per-query table of sub-vector dot products (``ops.sim_topk_pq``); the scores
 are approximate.
@@ -97,6 +100,22 @@ COMPRESSION_KEYS = ("type", "subvectors", "train_rows", "train_iterations")
 MAX_SUBVECTORS = 128
 MIN_PQ_ROWS = 256
 MAX_PQ_TRAIN_ROWS = 1048576
+#: those of ``index: {"type": "ivfpq"}`` (also in the contract)
+IVFPQ_ERRORS: Dict[str, str] = {
+    "ivfpq": ("payload.index of type 'ivfpq' must have an integer 'subvectors', a multiple of 4 up to 128 with corpus "
+              "dim / subvectors of 4, 8 or 16, and optional integers 'clusters' in [1, min(4096, train_rows)], 'nprobe' "
+              "in [1, min(32, clusters)], 'train_rows' in [256, min(corpus rows, 1048576)] and 'train_iterations' in "
+              "[1, 100]"),
+    "ivfpq_corpus": "payload.index of type 'ivfpq' needs payload.corpus_uri (a resident corpus)",
+    "ivfpq_metric": "payload.index of type 'ivfpq' needs metric 'cosine'",
+    "ivfpq_dim": "payload.index of type 'ivfpq' needs a corpus dim that is a multiple of 64 from 64 to 1024",
+    "ivfpq_rows": "payload.index of type 'ivfpq' needs a corpus of at least 256 rows",
+    "ivfpq_filter": "payload.index of type 'ivfpq' cannot be combined with payload.filter",
+    "ivfpq_compression": "payload.index of type 'ivfpq' cannot be combined with payload.compression (it holds the codes)",
+    "ivfpq_f16": "payload.index of type 'ivfpq' cannot be combined with corpus_dtype 'float16' (the codes are the resident form)",
+    "ivfpq_too_large": "ivfpq index slice exceeds SEARCH_INDEX_MAX_GB of codes and row ids",
+}
+IVFPQ_KEYS = ("type", "subvectors", "clusters", "nprobe", "train_rows", "train_iterations")
 
 
 class Options(NamedTuple):
@@ -109,6 +128,7 @@ class Options(NamedTuple):
     labels_uri: Optional[str] = None  # corpus_labels_uri, kept only when a label filter uses it
     index: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, train_iterations)
     compression: Optional[tuple] = None  # canonical: (subvectors, train_rows or None, train_iterations)
+    ivfpq: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, subvectors, train_rows or None, iterations)
 
 
 def _number(x: Any) -> bool:
@@ -192,6 +212,71 @@ def resolve_index(index: tuple, total: int) -> tuple:
     elif nprobe > clusters:
         raise ValueError(IVF_ERRORS["index"])
     return clusters, nprobe, t
+
+
+def parse_ivfpq(payload: Dict[str, Any], opt: Options) -> tuple:
+    """``payload.index`` of type ``ivfpq`` in canonical form, ``(clusters or None, nprobe or None, subvectors,
+    train_rows or None, train_iterations)``: everything about it that can be refused without the corpus
+    (:func:`resolve_ivfpq` does the rest)."""
+    ix = payload["index"]
+    if not set(ix) <= set(IVFPQ_KEYS):
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+
+    def integer(key, lo, hi, default):
+        if key not in ix:
+            return default
+        v = ix[key]
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError(IVFPQ_ERRORS["ivfpq"])
+        return v
+
+    canon = (integer("clusters", 1, MAX_CLUSTERS, None), integer("nprobe", 1, MAX_NPROBE, None),
+             integer("subvectors", 4, MAX_SUBVECTORS, None), integer("train_rows", MIN_PQ_ROWS, MAX_PQ_TRAIN_ROWS, None),
+             integer("train_iterations", 1, MAX_TRAIN_ITERATIONS, 10))
+    if canon[2] is None or canon[2] % 4 or (canon[0] is not None and canon[1] is not None and canon[1] > canon[0]):
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+    if "corpus_uri" not in payload:
+        raise ValueError(IVFPQ_ERRORS["ivfpq_corpus"])
+    if opt.metric != "cosine":
+        raise ValueError(IVFPQ_ERRORS["ivfpq_metric"])
+    if payload.get("corpus_dtype") == "float16":  # an explicit one; the environment's default does not apply to codes
+        raise ValueError(IVFPQ_ERRORS["ivfpq_f16"])
+    if "filter" in payload:
+        raise ValueError(IVFPQ_ERRORS["ivfpq_filter"])
+    if "compression" in payload:
+        raise ValueError(IVFPQ_ERRORS["ivfpq_compression"])
+    return canon
+
+
+def resolve_ivfpq(ivfpq: tuple, total: int, dim: int) -> tuple:
+    """(clusters, nprobe, subvectors, train_rows, train_iterations) of a canonical ``ivfpq`` for a corpus of ``total``
+    rows of ``dim`` columns: PQ's default ``train_rows = min(total, 65536)``, IVF's defaults ``ceil(sqrt(total))``
+    clusters (at most ``train_rows``: the centroids are trained on the sample) and ``nprobe = min(8, clusters)``, and
+    the bounds that need the corpus."""
+    from agent_tpu_amd.ops import pq_ok, sim_topk_ok
+    from agent_tpu_amd.runtime.ivf import default_clusters
+    from agent_tpu_amd.runtime.pq import default_train_rows
+
+    clusters, nprobe, M, T, t = ivfpq
+    if total < MIN_PQ_ROWS:
+        raise ValueError(IVFPQ_ERRORS["ivfpq_rows"])
+    if not sim_topk_ok(dim, 1):
+        raise ValueError(IVFPQ_ERRORS["ivfpq_dim"])
+    if not pq_ok(dim, M):
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+    if T is None:
+        T = default_train_rows(total)
+    elif T > total:
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+    if clusters is None:
+        clusters = min(default_clusters(total), T)
+    elif clusters > T:
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+    if nprobe is None:
+        nprobe = min(8, clusters)
+    elif nprobe > clusters:
+        raise ValueError(IVFPQ_ERRORS["ivfpq"])
+    return clusters, nprobe, M, T, t
 
 
 def parse_compression(payload: Dict[str, Any]) -> tuple:
@@ -294,6 +379,8 @@ def check_payload(payload: Dict[str, Any]) -> Options:
     if "filter" in payload:  # a job without one keeps its Options, its code path and its result keys
         flt, labels_uri = parse_filter(payload)
         opt = opt._replace(filter=flt, labels_uri=labels_uri)
+    if isinstance(payload.get("index"), dict) and payload["index"].get("type") == "ivfpq":  # a third path of its own
+        return opt._replace(ivfpq=parse_ivfpq(payload, opt))
     if "index" in payload:  # likewise: a job without one is untouched
         opt = opt._replace(index=parse_index(payload, opt))
     if "compression" in payload:  # likewise
@@ -489,6 +576,47 @@ def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric
     return s[:, :kk], i[:, :kk], total, cached, info
 
 
+def search_queries_ivfpq(device, qvecs, payload: Dict[str, Any], top_k: int, ivfpq: tuple, rank: int, ws: int):
+    """:func:`search_queries` through an IVF-PQ index (``runtime/ivfpq.py``), run as :func:`search_queries_pq`: every
+    rank trains the same centroids and codebooks from the same sample of the file (no collective), encodes its own
+    slice chunk by chunk and scans the probed clusters of its slice with ``id_base`` = the slice start; the lists,
+    already padded to ``top_k``, are all-gathered and merged. A row's score depends on the query, the centroids, the
+    codebooks and the row's codes only, and the union of the ranks' probed rows is the probed clusters of the whole
+    corpus, so the result has the same bits for every world size. -> (scores, ids on the host, padded to ``top_k``;
+    corpus rows; index_cached; the result's ``index`` dict) on rank 0, None elsewhere."""
+    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
+    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
+    from agent_tpu_amd.runtime import ivfpq as rt
+    from agent_tpu_amd.runtime import search as rs
+
+    exc, s, i, total, cached, info = None, None, None, 0, None, None
+    nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
+    try:
+        total, cdim = rs.corpus_shape(payload["corpus_uri"])
+        if cdim != dim:
+            raise ValueError(ERRORS["dim"])
+        clusters, nprobe, M, T, t = resolve_ivfpq(ivfpq, total, cdim)
+        s_r, n_r = split_range(0, total, ws, rank)
+        idx = rt.load_index(payload["corpus_uri"], s_r, n_r, device, clusters, M, T, t)
+        cached = idx.cached
+        info = {"type": "ivfpq", "clusters": clusters, "nprobe": nprobe, "subvectors": M, "train_rows": T,
+                "train_iterations": t, "converged": idx.converged, "bytes_per_row": M + 4}
+        maybe_inject_fault("search")
+        s, i, _ = rt.search(qvecs, idx, top_k, nprobe, id_base=s_r)
+    except Exception as e:
+        exc = e
+    counts = exchange_errors(exc, nq if s is not None else 0)
+    s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
+    if rank != 0:
+        return None
+    s, i = s.cpu(), i.cpu()
+    if ws > 1:  # as search_queries: every query's ws lists side by side -> merged; the padding sorts last
+        s = s.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        s, i = rs.merge_topk(s, i, top_k)
+    return s, i, total, cached, info
+
+
 def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str]], metric: str, pooling: str):
     """``[nq, dim]`` fp32 query vectors: the model's embeddings of ``queries``, or ``query_vectors``
     on the device (normalised there for cosine)."""
@@ -533,7 +661,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
     if cached is not None:
         out["index_cached"] = bool(cached)
     # default-path results keep their keys; a compressed corpus is resident as codes, whatever the default dtype
-    if "corpus_uri" in payload and opt.corpus_dtype != "float32" and compression_info is None:
+    codes_resident = compression_info is not None or (index_info or {}).get("type") == "ivfpq"
+    if "corpus_uri" in payload and opt.corpus_dtype != "float32" and not codes_resident:
         out["corpus_dtype"] = opt.corpus_dtype
     if filter_rows is not None:
         out["filter_rows"] = int(filter_rows)
@@ -573,6 +702,12 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
             raise ValueError(ERRORS["query_vectors"])
     if opt.index is not None:  # its own path, so that a job without an index stays as it was
         got = search_queries_ivf(device, qv, payload, opt.top_k, opt.index, rank, ws)
+        if got is None:
+            return None
+        s, i, total, cached, info = got
+        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, index_info=info)
+    if opt.ivfpq is not None:  # likewise
+        got = search_queries_ivfpq(device, qv, payload, opt.top_k, opt.ivfpq, rank, ws)
         if got is None:
             return None
         s, i, total, cached, info = got
@@ -621,6 +756,9 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
             if key.index is not None:  # the group shares the canonical index, nprobe included
                 got = search_queries_ivf(device, qv, first, K, key.index, rank, ws)
                 got = None if got is None else got[:4] + (None, got[4], None)
+            elif key.ivfpq is not None:  # the group shares the canonical ivfpq, nprobe included
+                got = search_queries_ivfpq(device, qv, first, K, key.ivfpq, rank, ws)
+                got = None if got is None else got[:4] + (None, got[4], None)
             elif key.compression is not None:  # the group shares the canonical compression
                 got = search_queries_pq(device, qv, first, K, key.metric, key.compression, rank, ws)
                 got = None if got is None else got[:4] + (None, None, got[4])
@@ -658,6 +796,9 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
         if opt.index is not None:  # (clusters, train_iterations) name the index; jobs that differ in nprobe probe
             clusters, nprobe, t = opt.index  # other rows per query, so they stay separate groups
             return group + ("ivf", clusters, t, nprobe)
+        if opt.ivfpq is not None:  # (clusters, subvectors, train_rows, train_iterations) name the index; nprobe
+            clusters, nprobe, M, T, t = opt.ivfpq  # separates groups, as for IVF
+            return group + ("ivfpq", clusters, M, T, t, nprobe)
         if opt.compression is not None:  # the canonical tuple names the codebooks and the codes
             return group + ("pq",) + opt.compression
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
