@@ -390,7 +390,21 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("lut"), py::arg("codes"), py::arg("row_ids"), py::arg("offsets"), py::arg("probes"), py::arg("coarse"),
       py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("M"), py::arg("k"), py::arg("K"), py::arg("nprobe"),
       py::arg("S"), py::arg("stream"));
-  m.def("kmeans_shape_ok", &kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
+  m.def("refine_chunks", &refine_chunks, "the chunk count refine_topk_partial runs for a wanted one (no empty chunk)",
+        py::arg("R"), py::arg("want"));
+  m.def(
+      "refine_topk_partial",
+      [](uintptr_t q, uintptr_t store, bool half, uintptr_t row_scale, uintptr_t cand, int cand_stride, uintptr_t ws,
+         int nq, int N, int D, int R, int k, int chunks, uintptr_t stream) {
+        refine_topk_partial(P<const float>(q), P<const void>(store), half, P<const float>(row_scale),
+                            P<const int32_t>(cand), cand_stride, P<float>(ws), nq, N, D, R, k, chunks, S(stream));
+      },
+      "exact scores of every query's own R candidate rows of an fp32 or fp16 store (device or pinned host memory): "
+      "every chunk's sorted top-k to ws [nq, P, k, 2]",
+      py::arg("q"), py::arg("store"), py::arg("half"), py::arg("row_scale"), py::arg("cand"), py::arg("cand_stride"),
+      py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("R"), py::arg("k"), py::arg("P"),
+      py::arg("stream"));
+  m.def("kmeans_shape_ok",&kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
   m.def(
       "kmeans_assign",
       [](uintptr_t x, uintptr_t c, uintptr_t bias, uintptr_t prev_labels, uintptr_t labels, uintptr_t best,

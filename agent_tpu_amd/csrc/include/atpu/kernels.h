@@ -238,6 +238,19 @@ void pq_scan_ivf_partial(const float* lut, const uint8_t* codes, const int32_t* 
                          const int64_t* probes, const float* coarse, float* ws, int nq, int N, int M, int k, int K,
                          int nprobe, int S, hipStream_t stream);
 
+// ---------------------------------------------------------------- shortlist re-scoring (sim_refine.hip)
+// refine_topk_partial: query i is scored against its own R candidate rows, cand[(i * R + j) * cand_stride] (int32 ids
+// into the store, distinct per query; an id outside [0, N) is an empty slot and is never dereferenced), with the bits
+// sim_topk gives the same (query, row): store [N, D] fp32, or fp16 (half) with an optional fp32 row_scale [N]. The
+// store may be pinned host memory given by its device-visible address; q, cand, row_scale and ws are device memory.
+// Every chunk's sorted top-k (value, row as int bits; empty: -inf, 0x7fffffff) goes to ws [nq, P, k, 2] for
+// sim_topk_merge, P = refine_chunks(R, wanted) <= kSimMaxSplits (no empty chunk). cand_stride 2 reads the row halves
+// of a scan workspace [nq, G, 32, 2] as they lie. D % 64 == 0, D in [64, 1024], k in [1, 32], R % 32 == 0,
+// R in [32, 8192], N < 2^31 - 256. Nothing outside store[0:N], row_scale[0:N] and the R slots of a query is read.
+int refine_chunks(int R, int want);
+void refine_topk_partial(const float* q, const void* store, bool half, const float* row_scale, const int32_t* cand,
+                         int cand_stride, float* ws, int nq, int N, int D, int R, int k, int P, hipStream_t stream);
+
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)
 // in the order of better() (score desc, centroid asc), best[i] that score; every score is one fp32

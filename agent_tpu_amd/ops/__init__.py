@@ -28,6 +28,8 @@ from .pq import (pq_ok, pq_encode, pq_encode_ref, pq_lut, pq_lut_ref, pq_scan_to
 from .pq import decode as pq_decode  # noqa: F401  (ops.decode stays the decode-attention module)
 from .pq_ivf import (pq_encode_residual, pq_encode_residual_ref, pq_coarse, pq_coarse_ref,  # noqa: F401
                      sim_topk_ivfpq, sim_topk_ivfpq_ref)
+from .refine import (refine_topk, refine_topk_ref, pq_scan_segments, pq_scan_segments_ref, segment_rows,  # noqa: F401
+                     shortlist_rows, candidates_ok)
 from .cluster import to_fixed  # noqa: F401
 from .cluster import (kmeans_assign, kmeans_assign_ref, kmeans_update, kmeans_update_ref, kmeans_finalize,  # noqa: F401
                       kmeans_finalize_ref, fixed_shift, fixed_sum, fixed_sum_ref, kmeans_ok)

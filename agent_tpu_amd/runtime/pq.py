@@ -44,6 +44,7 @@ class PqIndex(NamedTuple):
     start: int  # row of the file that slice row 0 is
     total: int  # rows of the whole file
     cached: bool = False  # served from the LRU
+    store: Optional[Any] = None  # runtime.refine.Store: the rows' originals for exact re-scoring (``refine``)
 
     @property
     def subvectors(self) -> int:
@@ -62,13 +63,19 @@ def sample_rows(total: int, T: int) -> torch.Tensor:
 
 def _rows_to_device(arr, lo: int, hi: int, normalize: bool, device: torch.device, index=None) -> torch.Tensor:
     """fp32 rows of the memory-mapped file on ``device``, checked and (for cosine) normalised."""
+    x = _raw_rows(arr, lo, hi, device, index)
+    return (rs.normalize_rows(x) if normalize else x).contiguous()
+
+
+def _raw_rows(arr, lo: int, hi: int, device: torch.device, index=None) -> torch.Tensor:
+    """fp32 rows of the memory-mapped file on ``device`` as stored, checked for finiteness."""
     import numpy as np
 
     src = arr[index] if index is not None else arr[lo:hi]
     x = torch.from_numpy(np.array(src, order="C")).to(device).to(torch.float32)  # a copy: only these rows are read
     if not bool(torch.isfinite(x).all()):
         raise ValueError(rs.ERRORS["corpus_nonfinite"])
-    return (rs.normalize_rows(x) if normalize else x).contiguous()
+    return x
 
 
 def train(sample: torch.Tensor, M: int, t: int) -> torch.Tensor:
@@ -109,8 +116,10 @@ def codes_bytes(count: int, M: int, device: torch.device) -> int:
     return rows * M
 
 
-def encode_slice(arr, start: int, count: int, books: torch.Tensor, normalize: bool, device: torch.device) -> torch.Tensor:
-    """The codes of rows ``[start, start + count)`` in the device's resident layout, chunk by chunk."""
+def encode_slice(arr, start: int, count: int, books: torch.Tensor, normalize: bool, device: torch.device,
+                 store=None) -> torch.Tensor:
+    """The codes of rows ``[start, start + count)`` in the device's resident layout, chunk by chunk. ``store`` (a
+    ``runtime.refine.Store``) is filled from the same chunks: the file is read once."""
     from .. import ops
     from ..ops.pq import BLOCK_ROWS
 
@@ -125,7 +134,11 @@ def encode_slice(arr, start: int, count: int, books: torch.Tensor, normalize: bo
     rows = max(BLOCK_ROWS, rs.CHUNK_BYTES // (dim * 4) // BLOCK_ROWS * BLOCK_ROWS)  # whole blocks per chunk
     for lo in range(0, count, rows):
         hi = min(lo + rows, count)
-        codes = ops.pq_encode(_rows_to_device(arr, start + lo, start + hi, normalize, device), books, bias)
+        raw = _raw_rows(arr, start + lo, start + hi, device)
+        x = (rs.normalize_rows(raw) if normalize else raw).contiguous()
+        if store is not None:
+            store.fill(lo, hi, raw, x)
+        codes = ops.pq_encode(x, books, bias)
         if cuda:
             part = ops.pq_interleave(codes).data
             out[lo // BLOCK_ROWS:lo // BLOCK_ROWS + part.shape[0]] = part
@@ -136,34 +149,44 @@ def encode_slice(arr, start: int, count: int, books: torch.Tensor, normalize: bo
 
 def load_index(uri: Any, start: int = 0, count: int = -1, device: torch.device = torch.device("cpu"),
                subvectors: int = 8, train_rows: Optional[int] = None, train_iterations: int = 10,
-               normalize: bool = True) -> PqIndex:
+               normalize: bool = True, refine: Optional[Tuple[str, str]] = None) -> PqIndex:
     """The cached index of rows ``[start, start + count)`` (``count < 0``: to the end) of the file, or a fresh
-    build. No collective: under DP every rank trains the same codebooks from the same sample."""
+    build. No collective: under DP every rank trains the same codebooks from the same sample. ``refine``
+    (``(vectors, store)``: ``runtime/refine.py``) adds the refine store of the slice to the entry, under a key of
+    its own: it is built, evicted and rebuilt with the codes."""
     from .. import ops
+    from . import refine as rf
 
     M, t = int(subvectors), int(train_iterations)
     total = rs.corpus_shape(uri)[0]
     T = default_train_rows(total) if train_rows is None else int(train_rows)
     key, arr, start, count, total, dim = _key(uri, start, count, device, M, T, t, normalize)
+    if refine is not None:
+        key = key + ("refine",) + tuple(refine)
     with rs._lock:
         hit = rs._cache.get(key)
         if hit is not None:
             rs._cache.move_to_end(key)
-            return PqIndex(hit[0], hit[1], count, start, total, True)
+            store = rf.Store(hit[2], hit[3]) if refine is not None else None
+            return PqIndex(hit[0], hit[1], count, start, total, True, store)
     if not ops.pq_ok(dim, M) or not MIN_ROWS <= T <= min(total, MAX_TRAIN_ROWS) or t < 1:
         raise ValueError("load_index: unsupported (dim, subvectors, train_rows, train_iterations)")
     if codes_bytes(count, M, device) > rs.max_bytes():  # before any allocation
         raise ValueError(ERRORS["compression_too_large"])
+    store = None
+    if refine is not None:  # sized before any allocation, as the codes
+        rf.check_size(count, dim, refine[0], refine[1], normalize, device, codes_bytes(count, M, device))
+        store = rf.allocate(count, dim, refine[0], refine[1], normalize, device)
     sample = _rows_to_device(arr, 0, 0, normalize, device, index=sample_rows(total, T).numpy())
     books = train(sample, M, t)
     del sample
-    codes = encode_slice(arr, start, count, books, normalize, device)
+    codes = encode_slice(arr, start, count, books, normalize, device, store)
     with rs._lock:
-        rs._cache[key] = (codes, books)
+        rs._cache[key] = (codes, books) if store is None else (codes, books, store.vectors, store.scale)
         rs._cache.move_to_end(key)
         while len(rs._cache) > rs.lru_capacity():
             rs._cache.popitem(last=False)
-    return PqIndex(codes, books, count, start, total, False)
+    return PqIndex(codes, books, count, start, total, False, store)
 
 
 def row_major_codes(index: PqIndex) -> torch.Tensor:

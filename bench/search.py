@@ -231,6 +231,7 @@ def pq_bench(a, ops, dev) -> int:
         x16 = x.half()
         del x
         resident = {"exact_f16": x16.numel() * 2, "pq": codes.data.numel() + books.numel() * 4, "pq_lut": 0}
+        store = None  # the refine arm's rows, made once per N
         for nq in a.queries:
             qs = [mixture(nq, centres) for _ in range(a.query_sets)]
 
@@ -273,7 +274,42 @@ def pq_bench(a, ops, dev) -> int:
                                       "mean_reconstruction_error": round(err, 4), "mixture_centres": K,
                                       "noise": a.ivf_noise, "query_sets": a.query_sets,
                                       "splits": a.splits or ops.pq.pq_auto_splits(N, dev)}), flush=True)
-        del x16, codes
+            for R in a.refine_candidates or ():
+                # exact re-scoring of a shortlist of R rows from the fp16 rows in --refine-store memory: the whole
+                # refined search (table, segmented scan, refine_topk), refine_topk alone on a ready shortlist, and
+                # the two arms above again, alternating. link_gbs: the bytes of the live shortlisted rows over the
+                # time of refine_topk alone.
+                if store is None:
+                    store = x16.cpu().pin_memory() if a.refine_store == "host" else x16
+                G = R // 32
+                cands = [ops.pq_scan_segments(ops.pq_lut(q, books), codes, G) for q in qs]
+
+                def refined(i):
+                    return ops.refine_topk(qs[i], store, ops.pq_scan_segments(ops.pq_lut(qs[i], books), codes, G), k)
+
+                def kernel(i):
+                    return ops.refine_topk(qs[i], store, cands[i], k)
+
+                hit = top1 = 0
+                for i in range(a.query_sets):
+                    ei, ai = exact(i)[1], refined(i)[1]
+                    hit += int((ai[:, :, None] == ei[:, None, :]).any(1).sum())
+                    top1 += int((ai[:, 0] == ei[:, 0]).sum())
+                live = ops.shortlist_rows(N, G)
+                for r in range(a.rounds):
+                    for variant, fn in (("refine", refined), ("refine_topk", kernel), ("pq", approx), ("exact_f16", exact)):
+                        us = timed(fn)
+                        print(json.dumps({"bench": "search_refine", "variant": variant, "N": N, "queries": nq, "dim": D,
+                                          "top_k": k, "subvectors": M, "candidates": R, "rescored_rows": live,
+                                          "store": a.refine_store, "vectors": "float16", "round": r,
+                                          "us_per_call": round(us, 2),
+                                          "link_gbs": round(nq * live * D * 2 / us / 1e3, 2) if variant == "refine_topk" else None,
+                                          "recall": round(hit / (a.query_sets * nq * k), 4),
+                                          "top1_agreement": round(top1 / (a.query_sets * nq), 4),
+                                          "recall_pq": round(recall, 4), "mixture_centres": K, "noise": a.ivf_noise,
+                                          "query_sets": a.query_sets,
+                                          "chunks": ops.refine.auto_chunks(nq, cands[0].shape[1], dev)}), flush=True)
+        del x16, codes, store
     return 0
 
 
@@ -368,6 +404,9 @@ def main() -> int:
                     help="run the product-quantization comparison with this many bytes per row instead")
     ap.add_argument("--ivfpq-clusters", type=int, default=0,
                     help="compare flat PQ, IVF fp32 and IVF-PQ with this many clusters instead (M from --pq-subvectors)")
+    ap.add_argument("--refine-candidates", type=int, nargs="+", default=None,
+                    help="with --pq-subvectors: also measure the refined search at these shortlist lengths")
+    ap.add_argument("--refine-store", choices=("host", "device"), default="host")
     ap.add_argument("--pq-train-rows", type=int, default=65536)
     ap.add_argument("--pq-train-iterations", type=int, default=10)
     a = ap.parse_args()

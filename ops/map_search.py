@@ -116,6 +116,20 @@ IVFPQ_ERRORS: Dict[str, str] = {
     "ivfpq_too_large": "ivfpq index slice exceeds SEARCH_INDEX_MAX_GB of codes and row ids",
 }
 IVFPQ_KEYS = ("type", "subvectors", "clusters", "nprobe", "train_rows", "train_iterations")
+#: those of ``refine`` (also in the contract)
+REFINE_ERRORS: Dict[str, str] = {
+    "refine": ("payload.refine must be {'candidates': R} with an integer R, a multiple of 32 from 32 to 8192 and at "
+               "least top_k, and optional 'vectors' of 'float16' or 'float32' and 'store' of 'host' or 'device'"),
+    "refine_compression": "payload.refine needs payload.compression (it re-scores the compressed search's shortlist)",
+    "refine_filter": "payload.refine cannot be combined with payload.filter",
+    "refine_index": "payload.refine cannot be combined with payload.index",
+    "refine_too_large": ("refine store of the corpus slice exceeds SEARCH_REFINE_MAX_GB of pinned host memory "
+                         "(store 'device': SEARCH_INDEX_MAX_GB together with the codes)"),
+}
+REFINE_KEYS = ("candidates", "vectors", "store")
+REFINE_VECTORS = ("float16", "float32")
+REFINE_STORES = ("host", "device")
+MAX_REFINE_CANDIDATES = 8192  # 32 * MAX_SPLITS: one list of 32 per segment
 
 
 class Options(NamedTuple):
@@ -129,6 +143,7 @@ class Options(NamedTuple):
     index: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, train_iterations)
     compression: Optional[tuple] = None  # canonical: (subvectors, train_rows or None, train_iterations)
     ivfpq: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, subvectors, train_rows or None, iterations)
+    refine: Optional[tuple] = None  # canonical: (candidates, vectors, store)
 
 
 def _number(x: Any) -> bool:
@@ -327,6 +342,25 @@ def resolve_compression(compression: tuple, total: int, dim: int) -> tuple:
     return M, T, t
 
 
+def parse_refine(payload: Dict[str, Any], opt: Options) -> tuple:
+    """``payload.refine`` in canonical form, ``(candidates, vectors, store)``; all of it can be refused without the
+    corpus."""
+    rf = payload["refine"]
+    if not isinstance(rf, dict) or not set(rf) <= set(REFINE_KEYS):
+        raise ValueError(REFINE_ERRORS["refine"])
+    R, vectors, store = rf.get("candidates"), rf.get("vectors", "float16"), rf.get("store", "host")
+    if not isinstance(R, int) or isinstance(R, bool) or R % 32 or not max(32, opt.top_k) <= R <= MAX_REFINE_CANDIDATES \
+            or vectors not in REFINE_VECTORS or store not in REFINE_STORES:
+        raise ValueError(REFINE_ERRORS["refine"])
+    if "filter" in payload:
+        raise ValueError(REFINE_ERRORS["refine_filter"])
+    if "index" in payload:
+        raise ValueError(REFINE_ERRORS["refine_index"])
+    if "compression" not in payload:
+        raise ValueError(REFINE_ERRORS["refine_compression"])
+    return R, vectors, store
+
+
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work."""
     top_k = payload.get("top_k", 10)
@@ -379,6 +413,8 @@ def check_payload(payload: Dict[str, Any]) -> Options:
     if "filter" in payload:  # a job without one keeps its Options, its code path and its result keys
         flt, labels_uri = parse_filter(payload)
         opt = opt._replace(filter=flt, labels_uri=labels_uri)
+    if "refine" in payload:  # likewise; refused before the forms it cannot join are looked at
+        opt = opt._replace(refine=parse_refine(payload, opt))
     if isinstance(payload.get("index"), dict) and payload["index"].get("type") == "ivfpq":  # a third path of its own
         return opt._replace(ivfpq=parse_ivfpq(payload, opt))
     if "index" in payload:  # likewise: a job without one is untouched
@@ -530,21 +566,28 @@ def search_queries_ivf(device, qvecs, payload: Dict[str, Any], top_k: int, index
 
 
 def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, compression: tuple, rank: int,
-                      ws: int):
+                      ws: int, refine: Optional[tuple] = None):
     """:func:`search_queries` over a product-quantized corpus (``runtime/pq.py``): every rank trains the same
     codebooks from the same sample of the file (no collective), encodes its own slice chunk by chunk and scans its
     codes with ``id_base`` = the slice start; the lists are padded to ``top_k``, all-gathered and merged as the exact
     ones are. A row's ADC score depends on the query, the codebooks and the row's codes only, so the result has the
     same bits for every world size. -> (scores, ids on the host; corpus rows; index_cached; the result's
-    ``compression`` dict) on rank 0, None elsewhere."""
+    ``compression`` dict; its ``refine`` dict or None) on rank 0, None elsewhere.
+
+    With ``refine`` (canonical form) every rank keeps the originals of its slice beside the codes
+    (``runtime/refine.py``), shortlists ``candidates`` rows of its own slice and re-scores them exactly; the lists
+    that are gathered hold exact scores. The shortlist is per rank slice: the result is a function of the payload
+    and the world size."""
     import torch
 
+    from agent_tpu_amd.ops import shortlist_rows
     from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
     from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
     from agent_tpu_amd.runtime import pq
+    from agent_tpu_amd.runtime import refine as rfn
     from agent_tpu_amd.runtime import search as rs
 
-    exc, s, i, total, cached, info = None, None, None, 0, None, None
+    exc, s, i, total, cached, info, rinfo = None, None, None, 0, None, None, None
     nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
     try:
         total, cdim = rs.corpus_shape(payload["corpus_uri"])
@@ -552,11 +595,19 @@ def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric
             raise ValueError(ERRORS["dim"])
         M, T, t = resolve_compression(compression, total, cdim)
         s_r, n_r = split_range(0, total, ws, rank)
-        idx = pq.load_index(payload["corpus_uri"], s_r, n_r, device, M, T, t, metric == "cosine")
-        cached = idx.cached
         info = {"type": "pq", "subvectors": M, "train_rows": T, "train_iterations": t, "bytes_per_row": M}
+        if refine is None:
+            idx = pq.load_index(payload["corpus_uri"], s_r, n_r, device, M, T, t, metric == "cosine")
+        else:
+            idx = pq.load_index(payload["corpus_uri"], s_r, n_r, device, M, T, t, metric == "cosine", refine=refine[1:])
+            rows = sum(shortlist_rows(n, refine[0] // 32) for n in (split_range(0, total, ws, r)[1] for r in range(ws)) if n)
+            rinfo = {"candidates": refine[0], "vectors": refine[1], "store": refine[2], "rescored_rows": rows}
+        cached = idx.cached
         maybe_inject_fault("search")
-        s, i = pq.search(qvecs, idx, top_k, id_base=s_r)
+        if refine is None:
+            s, i = pq.search(qvecs, idx, top_k, id_base=s_r)
+        else:
+            s, i, _ = rfn.search(qvecs, idx, top_k, refine[0], id_base=s_r)
         if s.shape[1] < top_k:  # a slice shorter than top_k: pad, so every rank gathers [nq, top_k]
             pad = top_k - s.shape[1]
             s = torch.cat([s, torch.full((nq, pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
@@ -573,7 +624,7 @@ def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric
         i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
         s, i = rs.merge_topk(s, i, top_k)
     kk = min(top_k, total)
-    return s[:, :kk], i[:, :kk], total, cached, info
+    return s[:, :kk], i[:, :kk], total, cached, info, rinfo
 
 
 def search_queries_ivfpq(device, qvecs, payload: Dict[str, Any], top_k: int, ivfpq: tuple, rank: int, ws: int):
@@ -633,7 +684,8 @@ def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str
 
 def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim: int, cached: Optional[bool],
            ws: int, filter_rows: Optional[int] = None, index_info: Optional[Dict[str, Any]] = None,
-           compression_info: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+           compression_info: Optional[Dict[str, Any]] = None, refine_info: Optional[Dict[str, Any]] = None
+           ) -> Dict[str, Any]:
     """One job's result from its rows of the merged lists (rank 0): the first ``top_k`` entries (with
     a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host.
     ``filter_rows``: the corpus rows that passed the job's filter (None: no filter). ``index_info``: the
@@ -670,6 +722,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         out["index"] = dict(index_info)
     if compression_info is not None:
         out["compression"] = dict(compression_info)
+    if refine_info is not None:
+        out["refine"] = dict(refine_info)
     out.update(ids=ids_l, scores=sc_l)
     return out
 
@@ -713,11 +767,12 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         s, i, total, cached, info = got
         return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, index_info=info)
     if opt.compression is not None:  # likewise
-        got = search_queries_pq(device, qv, payload, opt.top_k, opt.metric, opt.compression, rank, ws)
+        got = search_queries_pq(device, qv, payload, opt.top_k, opt.metric, opt.compression, rank, ws, opt.refine)
         if got is None:
             return None
-        s, i, total, cached, info = got
-        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info)
+        s, i, total, cached, info, rinfo = got
+        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info,
+                      refine_info=rinfo)
     got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
                          opt.filter, opt.labels_uri)
     if got is None:
@@ -755,27 +810,27 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 qv = torch.cat([h.engine.embed_texts(ts, key.pooling, key.metric == "cosine").emb for _, _, ts in jobs])
             if key.index is not None:  # the group shares the canonical index, nprobe included
                 got = search_queries_ivf(device, qv, first, K, key.index, rank, ws)
-                got = None if got is None else got[:4] + (None, got[4], None)
+                got = None if got is None else got[:4] + (None, got[4], None, None)
             elif key.ivfpq is not None:  # the group shares the canonical ivfpq, nprobe included
                 got = search_queries_ivfpq(device, qv, first, K, key.ivfpq, rank, ws)
-                got = None if got is None else got[:4] + (None, got[4], None)
-            elif key.compression is not None:  # the group shares the canonical compression
-                got = search_queries_pq(device, qv, first, K, key.metric, key.compression, rank, ws)
-                got = None if got is None else got[:4] + (None, None, got[4])
+                got = None if got is None else got[:4] + (None, got[4], None, None)
+            elif key.compression is not None:  # the group shares the canonical compression and the canonical refine
+                got = search_queries_pq(device, qv, first, K, key.metric, key.compression, rank, ws, key.refine)
+                got = None if got is None else got[:4] + (None, None, got[4], got[5])
             else:
                 got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
                                      key.filter, key.labels_uri)
-                got = None if got is None else got + (None, None)
+                got = None if got is None else got + (None, None, None)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
                 out[n] = ("err", exc)
             return out if rank == 0 else None
         if got is not None:
-            s, i, total, cached, filter_rows, info, cinfo = got
+            s, i, total, cached, filter_rows, info, cinfo, rinfo = got
             pos = 0
             for n, opt, ts in jobs:
                 out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
-                                       int(qv.shape[1]), cached, ws, filter_rows, info, cinfo))
+                                       int(qv.shape[1]), cached, ws, filter_rows, info, cinfo, rinfo))
                 pos += len(ts)
     return out if rank == 0 else None
 
@@ -799,7 +854,9 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
         if opt.ivfpq is not None:  # (clusters, subvectors, train_rows, train_iterations) name the index; nprobe
             clusters, nprobe, M, T, t = opt.ivfpq  # separates groups, as for IVF
             return group + ("ivfpq", clusters, M, T, t, nprobe)
-        if opt.compression is not None:  # the canonical tuple names the codebooks and the codes
+        if opt.compression is not None:  # the canonical tuple names the codebooks and the codes; jobs that differ in
+            if opt.refine is not None:  # refine re-score other shortlists from other stores: separate groups
+                return group + ("pq",) + opt.compression + ("refine",) + opt.refine
             return group + ("pq",) + opt.compression
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
