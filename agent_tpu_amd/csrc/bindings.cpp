@@ -390,6 +390,27 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("lut"), py::arg("codes"), py::arg("row_ids"), py::arg("offsets"), py::arg("probes"), py::arg("coarse"),
       py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("M"), py::arg("k"), py::arg("K"), py::arg("nprobe"),
       py::arg("S"), py::arg("stream"));
+  m.def("binary_shape_ok", &binary_shape_ok, "dims the binary-corpus kernels take", py::arg("D"));
+  m.def(
+      "binary_pack",
+      [](uintptr_t x, uintptr_t thr, uintptr_t out, int64_t n, int D, bool interleave, uintptr_t stream) {
+        binary_pack(P<const float>(x), P<const float>(thr), P<uint32_t>(out), n, D, interleave, S(stream));
+      },
+      "sign bits x > thr of x [n, D] as uint32 words: row-major [n, D / 32] or the scan layout [ceil(n / 64), D / 32, 64]",
+      py::arg("x"), py::arg("thr"), py::arg("out"), py::arg("n"), py::arg("D"), py::arg("interleave"), py::arg("stream"));
+  m.def("hamming_scan_items", &hamming_scan_items, "work items (segments * parts) per query of hamming_scan_partial",
+        py::arg("N"), py::arg("seg_blocks"), py::arg("parts"));
+  m.def(
+      "hamming_scan_partial",
+      [](uintptr_t qbits, uintptr_t codes, uintptr_t ws, int nq, int N, int D, int k, int seg_blocks, int parts,
+         uintptr_t stream) {
+        hamming_scan_partial(P<const uint32_t>(qbits), P<const uint32_t>(codes), P<float>(ws), nq, N, D, k, seg_blocks,
+                             parts, S(stream));
+      },
+      "row-stationary Hamming scan of binary codes: the sorted top-k of every (query, segment, part) to "
+      "ws [nq, items, k, 2]",
+      py::arg("qbits"), py::arg("codes"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("k"),
+      py::arg("seg_blocks"), py::arg("parts"), py::arg("stream"));
   m.def("refine_chunks", &refine_chunks, "the chunk count refine_topk_partial runs for a wanted one (no empty chunk)",
         py::arg("R"), py::arg("want"));
   m.def(

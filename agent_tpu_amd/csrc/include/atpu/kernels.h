@@ -251,6 +251,26 @@ int refine_chunks(int R, int want);
 void refine_topk_partial(const float* q, const void* store, bool half, const float* row_scale, const int32_t* cand,
                          int cand_stride, float* ws, int nq, int N, int D, int R, int k, int P, hipStream_t stream);
 
+// ---------------------------------------------------------------- binary corpus (sim_binary.hip)
+// A row of D floats as D bits: bit b of word w (uint32) of a row = x[row, 32 w + b] > thr[32 w + b] (a plain
+// comparison: -0.0, +0.0 and NaN give 0 against a zero threshold). W = D / 32, D % 64 == 0, D in [64, 1024].
+// binary_pack: x [n, D] fp32, thr [D] fp32 -> words, row-major [n, W], or (interleave) the scan layout
+// [ceil(n / 64)][W][64] with word (b, w, lane) = bits(64 b + lane, w), the rows past n of the last block zero: the
+// bytes of pq.hip's interleaved codes at M = 4 W.
+// hamming_scan_partial: score(i, r) = D - 2 popcount(qbits[i] xor bits(r)) as fp32, the exact +-1 dot product. The
+// rows are cut into segments of seg_blocks 64-row blocks and every segment into `parts` pieces; the sorted top-k
+// (value, row as int bits; empty: -inf, 0x7fffffff) of (query, segment, part) goes to
+// ws [nq, items, k, 2], items = hamming_scan_items(N, seg_blocks, parts) = segments * parts, every slot written, for
+// sim_topk_merge (the plain search: one segment, P = parts; per-segment lists: nq * segments "queries" of P = parts).
+// qbits [nq, W] row-major, codes in the scan layout. k in [1, 32], parts in [1, kSimMaxSplits], N < 2^31 - 256.
+// Nothing outside these tensors is touched.
+bool binary_shape_ok(int D);
+void binary_pack(const float* x, const float* thr, uint32_t* out, int64_t n, int D, bool interleave,
+                 hipStream_t stream);
+int hamming_scan_items(int N, int seg_blocks, int parts);
+void hamming_scan_partial(const uint32_t* qbits, const uint32_t* codes, float* ws, int nq, int N, int D, int k,
+                          int seg_blocks, int parts, hipStream_t stream);
+
 // ---------------------------------------------------------------- k-means (kmeans.hip)
 // Assignment step: labels[i] = arg-max over k of dot(x[i], c[k]) (+ bias[k], one fp32 add; nullptr = none)
 // in the order of better() (score desc, centroid asc), best[i] that score; every score is one fp32

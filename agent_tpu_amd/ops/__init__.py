@@ -30,6 +30,9 @@ from .pq_ivf import (pq_encode_residual, pq_encode_residual_ref, pq_coarse, pq_c
                      sim_topk_ivfpq, sim_topk_ivfpq_ref)
 from .refine import (refine_topk, refine_topk_ref, pq_scan_segments, pq_scan_segments_ref, segment_rows,  # noqa: F401
                      shortlist_rows, candidates_ok)
+from .binary import (binary_ok, binary_pack, binary_pack_ref, hamming_scan_topk, hamming_scan_topk_ref,  # noqa: F401
+                     hamming_scan_segments, hamming_scan_segments_ref, sim_topk_binary, sim_topk_binary_ref,
+                     binary_interleave, binary_deinterleave, BinaryCodes)
 from .cluster import to_fixed  # noqa: F401
 from .cluster import (kmeans_assign, kmeans_assign_ref, kmeans_update, kmeans_update_ref, kmeans_finalize,  # noqa: F401
                       kmeans_finalize_ref, fixed_shift, fixed_sum, fixed_sum_ref, kmeans_ok)

@@ -27,6 +27,10 @@ the build time and the probe-and-plan time; one JSON line per (N, queries, nprob
 search and ``ops.sim_topk_pq`` over ``M``-byte codes of the same rows, alternating, with the resident bytes of
 both, recall against the exact result and the training and encoding times; one JSON line per (N, queries, variant,
 round).
+
+``--binary`` measures the binary (sign-bit) search instead (:func:`binary_bench`): ``ops.sim_topk_binary``, the PQ
+search at ``M = dim / 8`` and the exact fp16 search on the same rows, alternating; with ``--refine-candidates`` the
+two refined searches as well.
 """
 from __future__ import annotations
 
@@ -313,6 +317,89 @@ def pq_bench(a, ops, dev) -> int:
     return 0
 
 
+def binary_bench(a, ops, dev) -> int:
+    """``--binary``: the binary (sign-bit, zero threshold) search against the PQ search at ``M = dim / 8`` (the same
+    bytes per row) and the exact fp16-resident one, on :func:`pq_bench`'s seeded mixture and with its protocol: per
+    (N, queries) the arms ``binary`` (``ops.sim_topk_binary``: pack, Hamming scan, merge), ``pq`` and ``exact_f16``
+    alternate for ``--rounds`` rounds over ``--query-sets`` rotating query batches. With ``--refine-candidates R`` the
+    refined searches ``refine_binary`` (pack, ``hamming_scan_segments``, ``refine_topk``) and ``refine_pq`` (table,
+    ``pq_scan_segments``, ``refine_topk``) alternate with the same three, the fp16 rows in ``--refine-store`` memory.
+    ``recall`` / ``top1_agreement`` are against the exact fp16 top-k."""
+    from agent_tpu_amd.runtime import pq
+    from agent_tpu_amd.runtime.search import CHUNK_BYTES, normalize_rows
+
+    D, k, M = a.dim, a.top_k, a.dim // 8
+    K = a.ivf_clusters or 1024
+    gen = torch.Generator(device=dev).manual_seed(0)
+    thr = torch.zeros(D, device=dev)
+
+    def mixture(n, centres):
+        pick = torch.randint(0, centres.shape[0], (n,), device=dev, generator=gen)
+        return normalize_rows(centres[pick] + a.ivf_noise * torch.randn(n, D, device=dev, generator=gen)).contiguous()
+
+    for N in a.rows:
+        centres = normalize_rows(torch.randn(K, D, device=dev, generator=gen))
+        x = mixture(N, centres)
+        books = pq.train(x[pq.sample_rows(N, min(N, a.pq_train_rows)).to(dev)].contiguous(), M, a.pq_train_iterations)
+        bias = ops.pq_bias(books)
+        rows = max(64, CHUNK_BYTES // (D * 4) // 64 * 64)
+        codes = ops.pq_interleave(torch.cat([ops.pq_encode(x[lo:lo + rows], books, bias) for lo in range(0, N, rows)]))
+        bits = ops.BinaryCodes(torch.cat([ops.binary_pack(x[lo:lo + rows], thr, True).data for lo in range(0, N, rows)]), N, D)
+        x16 = x.half()
+        del x
+        store = None
+        for nq in a.queries:
+            qs = [mixture(nq, centres) for _ in range(a.query_sets)]
+            arms = {"binary": lambda i: ops.sim_topk_binary(qs[i], thr, bits, k, splits=a.splits or None),
+                    "pq": lambda i: ops.sim_topk_pq(qs[i], books, codes, k, splits=a.splits or None),
+                    "exact_f16": lambda i: ops.sim_topk(qs[i], x16, k, splits=a.splits or None)}
+
+            def timed(fn):
+                for i in range(a.query_sets):
+                    fn(i)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for it in range(a.iters):
+                    fn(it % a.query_sets)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                return e0.elapsed_time(e1) * 1e3 / a.iters  # us per call
+
+            def agreement(fn):
+                hit = top1 = 0
+                for i in range(a.query_sets):
+                    ei, ai = arms["exact_f16"](i)[1], fn(i)[1]
+                    hit += int((ai[:, :, None] == ei[:, None, :]).any(1).sum())
+                    top1 += int((ai[:, 0] == ei[:, 0]).sum())
+                return round(hit / (a.query_sets * nq * k), 4), round(top1 / (a.query_sets * nq), 4)
+
+            def report(bench, names, extra):
+                acc = {v: agreement(arms[v]) for v in names}
+                for r in range(a.rounds):
+                    for v in names:
+                        print(json.dumps(dict({"bench": bench, "variant": v, "N": N, "queries": nq, "dim": D, "top_k": k,
+                                               "bytes_per_row": 2 * D if v == "exact_f16" else M, "round": r,
+                                               "us_per_call": round(timed(arms[v]), 2), "recall": acc[v][0],
+                                               "top1_agreement": acc[v][1], "mixture_centres": K, "noise": a.ivf_noise,
+                                               "query_sets": a.query_sets}, **extra)), flush=True)
+
+            report("search_binary", ("binary", "pq", "exact_f16"), {})
+            for R in a.refine_candidates or ():
+                if store is None:
+                    store = x16.cpu().pin_memory() if a.refine_store == "host" else x16
+                G = R // 32
+                arms["refine_binary"] = lambda i: ops.refine_topk(
+                    qs[i], store, ops.hamming_scan_segments(ops.binary_pack(qs[i], thr), bits, D, G), k)
+                arms["refine_pq"] = lambda i: ops.refine_topk(
+                    qs[i], store, ops.pq_scan_segments(ops.pq_lut(qs[i], books), codes, G), k)
+                report("search_binary_refine", ("refine_binary", "refine_pq", "binary", "pq", "exact_f16"),
+                       {"candidates": R, "rescored_rows": ops.shortlist_rows(N, G), "store": a.refine_store,
+                        "vectors": "float16"})
+        del x16, codes, bits, store
+    return 0
+
+
 def ivfpq_bench(a, ops, dev) -> int:
     """``--ivfpq-clusters K`` (with ``--pq-subvectors M``): flat PQ, IVF fp32 and IVF-PQ on the same seeded mixture
     corpus (``K`` centres, ``--ivf-noise``), ``M`` and ``--nprobe`` values. The three indexes are built from in-memory
@@ -404,8 +491,10 @@ def main() -> int:
                     help="run the product-quantization comparison with this many bytes per row instead")
     ap.add_argument("--ivfpq-clusters", type=int, default=0,
                     help="compare flat PQ, IVF fp32 and IVF-PQ with this many clusters instead (M from --pq-subvectors)")
+    ap.add_argument("--binary", action="store_true",
+                    help="compare the binary (sign-bit) search with PQ at M = dim / 8 and the exact fp16 search instead")
     ap.add_argument("--refine-candidates", type=int, nargs="+", default=None,
-                    help="with --pq-subvectors: also measure the refined search at these shortlist lengths")
+                    help="with --pq-subvectors or --binary: also measure the refined search at these shortlist lengths")
     ap.add_argument("--refine-store", choices=("host", "device"), default="host")
     ap.add_argument("--pq-train-rows", type=int, default=65536)
     ap.add_argument("--pq-train-iterations", type=int, default=10)
@@ -420,6 +509,8 @@ def main() -> int:
         return filter_bench(a, ops, dev)
     if a.ivfpq_clusters:
         return ivfpq_bench(a, ops, dev)
+    if a.binary:
+        return binary_bench(a, ops, dev)
     if a.pq_subvectors:
         return pq_bench(a, ops, dev)
     if a.ivf_clusters:

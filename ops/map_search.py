@@ -15,7 +15,9 @@ product-quantization codes of the residuals, every query scored against the code
 (``ops.sim_topk_ivfpq``).
 ``compression`` keeps the corpus product-quantized (``agent_tpu_amd/runtime/pq.py``): ``subvectors`` bytes per row
 instead of ``4 dim``, scored from a per-query table of sub-vector dot products (``ops.sim_topk_pq``); the scores
-are approximate.
+are approximate. ``compression`` of type ``binary`` keeps one bit per dimension instead (``agent_tpu_amd/runtime/binary.py``):
+``dim / 8`` bytes per row, scored by the Hamming distance against the query's bits (``ops.sim_topk_binary``); with
+``refine`` its shortlist is re-scored exactly.
 
 Under ``torchrun`` every rank embeds the queries, searches its slice of the corpus, and rank 0
 merges the per-rank lists in the same total order (score descending, id ascending). Errors are
@@ -100,6 +102,19 @@ COMPRESSION_KEYS = ("type", "subvectors", "train_rows", "train_iterations")
 MAX_SUBVECTORS = 128
 MIN_PQ_ROWS = 256
 MAX_PQ_TRAIN_ROWS = 1048576
+#: those of ``compression: {"type": "binary"}`` (also in the contract)
+BINARY_ERRORS: Dict[str, str] = {
+    "binary": "payload.compression of type 'binary' must be {'type': 'binary'} with an optional 'threshold' of 'zero' or 'mean'",
+    "binary_corpus": "payload.compression of type 'binary' needs payload.corpus_uri (a resident corpus)",
+    "binary_f16": ("payload.compression of type 'binary' cannot be combined with corpus_dtype 'float16' (the bits are the "
+                   "resident form)"),
+    "binary_filter": "payload.compression of type 'binary' cannot be combined with payload.filter",
+    "binary_index": "payload.compression of type 'binary' cannot be combined with payload.index",
+    "binary_dim": "payload.compression of type 'binary' needs a corpus dim that is a multiple of 64 from 64 to 1024",
+    "binary_too_large": "binary corpus slice exceeds SEARCH_INDEX_MAX_GB of codes",
+}
+BINARY_KEYS = ("type", "threshold")
+BINARY_THRESHOLDS = ("zero", "mean")
 #: those of ``index: {"type": "ivfpq"}`` (also in the contract)
 IVFPQ_ERRORS: Dict[str, str] = {
     "ivfpq": ("payload.index of type 'ivfpq' must have an integer 'subvectors', a multiple of 4 up to 128 with corpus "
@@ -144,6 +159,7 @@ class Options(NamedTuple):
     compression: Optional[tuple] = None  # canonical: (subvectors, train_rows or None, train_iterations)
     ivfpq: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, subvectors, train_rows or None, iterations)
     refine: Optional[tuple] = None  # canonical: (candidates, vectors, store)
+    binary: Optional[tuple] = None  # canonical: (threshold,)
 
 
 def _number(x: Any) -> bool:
@@ -324,6 +340,23 @@ def parse_compression(payload: Dict[str, Any]) -> tuple:
     return canon
 
 
+def parse_binary(payload: Dict[str, Any]) -> tuple:
+    """``payload.compression`` of type ``binary`` in canonical form, ``(threshold,)``: everything about it that can be
+    refused without the corpus (the corpus dim is checked when the file is opened, before any device work)."""
+    cp = payload["compression"]
+    if not set(cp) <= set(BINARY_KEYS) or cp.get("threshold", "zero") not in BINARY_THRESHOLDS:
+        raise ValueError(BINARY_ERRORS["binary"])
+    if "corpus_uri" not in payload:
+        raise ValueError(BINARY_ERRORS["binary_corpus"])
+    if payload.get("corpus_dtype") == "float16":  # an explicit one; the environment's default does not apply to codes
+        raise ValueError(BINARY_ERRORS["binary_f16"])
+    if "filter" in payload:
+        raise ValueError(BINARY_ERRORS["binary_filter"])
+    if "index" in payload:
+        raise ValueError(BINARY_ERRORS["binary_index"])
+    return (cp.get("threshold", "zero"),)
+
+
 def resolve_compression(compression: tuple, total: int, dim: int) -> tuple:
     """(subvectors, train_rows, train_iterations) of a canonical ``compression`` for a corpus of ``total`` rows of
     ``dim`` columns: the default ``train_rows = min(total, 65536)`` and the bounds that need the corpus."""
@@ -419,6 +452,9 @@ def check_payload(payload: Dict[str, Any]) -> Options:
         return opt._replace(ivfpq=parse_ivfpq(payload, opt))
     if "index" in payload:  # likewise: a job without one is untouched
         opt = opt._replace(index=parse_index(payload, opt))
+    cp = payload.get("compression")
+    if isinstance(cp, dict) and isinstance(cp.get("type"), str) and cp["type"] == "binary":  # a path of its own beside PQ
+        return opt._replace(binary=parse_binary(payload))
     if "compression" in payload:  # likewise
         opt = opt._replace(compression=parse_compression(payload))
     return opt
@@ -627,6 +663,63 @@ def search_queries_pq(device, qvecs, payload: Dict[str, Any], top_k: int, metric
     return s[:, :kk], i[:, :kk], total, cached, info, rinfo
 
 
+def search_queries_binary(device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, binary: tuple, rank: int,
+                          ws: int, refine: Optional[tuple] = None):
+    """:func:`search_queries` over a binary corpus (``runtime/binary.py``), run as :func:`search_queries_pq`: every rank
+    derives the same threshold from the same sample of the file (no collective), packs its own slice chunk by chunk
+    and scans its bits with ``id_base`` = the slice start; the lists are padded to ``top_k``, all-gathered and merged
+    as the exact ones are. A row's score is an integer that depends on the query's and the row's bits only, so the
+    result has the same bits for every world size. With ``refine`` every rank shortlists ``candidates`` rows of its
+    own slice and re-scores them exactly, as for PQ. -> (scores, ids on the host; corpus rows; index_cached; the
+    result's ``compression`` dict; its ``refine`` dict or None) on rank 0, None elsewhere."""
+    import torch
+
+    from agent_tpu_amd.ops import binary_ok, shortlist_rows
+    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
+    from agent_tpu_amd.parallel.dp_ops import exchange_errors, maybe_inject_fault
+    from agent_tpu_amd.runtime import binary as rb
+    from agent_tpu_amd.runtime import search as rs
+
+    exc, s, i, total, cached, info, rinfo = None, None, None, 0, None, None, None
+    nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
+    try:
+        total, cdim = rs.corpus_shape(payload["corpus_uri"])
+        if cdim != dim:
+            raise ValueError(ERRORS["dim"])
+        if not binary_ok(cdim):
+            raise ValueError(BINARY_ERRORS["binary_dim"])
+        s_r, n_r = split_range(0, total, ws, rank)
+        info = {"type": "binary", "threshold": binary[0], "bits": cdim, "bytes_per_row": cdim // 8}
+        idx = rb.load_index(payload["corpus_uri"], s_r, n_r, device, binary[0], metric == "cosine",
+                            refine=None if refine is None else refine[1:])
+        if refine is not None:
+            rows = sum(shortlist_rows(n, refine[0] // 32) for n in (split_range(0, total, ws, r)[1] for r in range(ws)) if n)
+            rinfo = {"candidates": refine[0], "vectors": refine[1], "store": refine[2], "rescored_rows": rows}
+        cached = idx.cached
+        maybe_inject_fault("search")
+        if refine is None:
+            s, i = rb.search(qvecs, idx, top_k, id_base=s_r)
+        else:
+            s, i, _ = rb.search_refined(qvecs, idx, top_k, refine[0], id_base=s_r)
+        if s.shape[1] < top_k:  # a slice shorter than top_k: pad, so every rank gathers [nq, top_k]
+            pad = top_k - s.shape[1]
+            s = torch.cat([s, torch.full((nq, pad), float("-inf"), dtype=s.dtype, device=s.device)], 1)
+            i = torch.cat([i, torch.full((nq, pad), PAD_ID, dtype=i.dtype, device=i.device)], 1)
+    except Exception as e:
+        exc = e
+    counts = exchange_errors(exc, nq if s is not None else 0)
+    s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
+    if rank != 0:
+        return None
+    s, i = s.cpu(), i.cpu()
+    if ws > 1:  # as search_queries: every query's ws lists side by side -> merged; the padding sorts last
+        s = s.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        i = i.view(ws, nq, top_k).permute(1, 0, 2).reshape(nq, ws * top_k)
+        s, i = rs.merge_topk(s, i, top_k)
+    kk = min(top_k, total)
+    return s[:, :kk], i[:, :kk], total, cached, info, rinfo
+
+
 def search_queries_ivfpq(device, qvecs, payload: Dict[str, Any], top_k: int, ivfpq: tuple, rank: int, ws: int):
     """:func:`search_queries` through an IVF-PQ index (``runtime/ivfpq.py``), run as :func:`search_queries_pq`: every
     rank trains the same centroids and codebooks from the same sample of the file (no collective), encodes its own
@@ -773,6 +866,13 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         s, i, total, cached, info, rinfo = got
         return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info,
                       refine_info=rinfo)
+    if opt.binary is not None:  # likewise
+        got = search_queries_binary(device, qv, payload, opt.top_k, opt.metric, opt.binary, rank, ws, opt.refine)
+        if got is None:
+            return None
+        s, i, total, cached, info, rinfo = got
+        return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info,
+                      refine_info=rinfo)
     got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
                          opt.filter, opt.labels_uri)
     if got is None:
@@ -817,6 +917,9 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
             elif key.compression is not None:  # the group shares the canonical compression and the canonical refine
                 got = search_queries_pq(device, qv, first, K, key.metric, key.compression, rank, ws, key.refine)
                 got = None if got is None else got[:4] + (None, None, got[4], got[5])
+            elif key.binary is not None:  # the group shares the threshold and the canonical refine
+                got = search_queries_binary(device, qv, first, K, key.metric, key.binary, rank, ws, key.refine)
+                got = None if got is None else got[:4] + (None, None, got[4], got[5])
             else:
                 got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
                                      key.filter, key.labels_uri)
@@ -858,6 +961,8 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
             if opt.refine is not None:  # refine re-score other shortlists from other stores: separate groups
                 return group + ("pq",) + opt.compression + ("refine",) + opt.refine
             return group + ("pq",) + opt.compression
+        if opt.binary is not None:  # the threshold names the bits; binary jobs never group with PQ jobs
+            return group + ("binary",) + opt.binary + ((("refine",) + opt.refine) if opt.refine is not None else ())
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
     return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
