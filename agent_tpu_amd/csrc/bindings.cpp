@@ -733,6 +733,16 @@ PYBIND11_MODULE(_atpu, m) {
     vocab_topk_merge(P<const float>(ws), P<const int32_t>(valid), P<const float>(lse_in), P<int32_t>(tok),
                      P<float>(logit), P<float>(prob), P<float>(lse), R, V, k, S(stream));
   });
+  m.def("term_max", [](uintptr_t t, uintptr_t lens, uintptr_t E, uintptr_t xmax, int B, int Sq, int V, int H,
+                       int vocab_tile, uintptr_t stream) {
+    term_max(P<const bf16>(t), P<const int32_t>(lens), P<const bf16>(E), P<float>(xmax), B, Sq, V, H, vocab_tile,
+             S(stream));
+  });
+  m.def("term_select", [](uintptr_t xmax, uintptr_t bias, uintptr_t tok, uintptr_t xs, uintptr_t w, uintptr_t nnz,
+                          int B, int V, int k, uintptr_t stream) {
+    term_select(P<const float>(xmax), P<const float>(bias), P<int32_t>(tok), P<float>(xs), P<float>(w),
+                P<int32_t>(nnz), B, V, k, S(stream));
+  });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

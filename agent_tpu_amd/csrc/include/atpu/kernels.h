@@ -622,6 +622,21 @@ void vocab_topk_partial(const float* t, const bf16* E, const float* bias, float*
 void vocab_topk_merge(const float* ws, const int32_t* valid, const float* lse_in, int32_t* tok, float* logit,
                       float* prob, float* lse, int R, int V, int k, hipStream_t stream);
 
+// ------------------------------------------- learned sparse term weights (sparse_head.hip)
+// xmax [B, V] fp32 = max over the live tokens i < lens[b] of t[b * S + i] . E[v] (t [B*S, H] and
+// E [V, H] bf16 on the bf16 MFMA, one fp32 accumulator per (token, entry), the k order a function
+// of H alone; -inf when lens[b] <= 0; lens is clamped to S). Rows of padding tokens are never
+// loaded. vocab_tile: 64 or 32 entries of E per workgroup (0: the default, 64); the result has the
+// same bits for both. H % 64 == 0 in [64, 1024], S in [1, 512], V >= 1, B >= 1.
+void term_max(const bf16* t, const int32_t* lens, const bf16* E, float* xmax, int B, int S, int V, int H,
+              int vocab_tile, hipStream_t stream);
+// Per text b: x[v] = xmax[b, v] + bias[v]; the terms are the entries with x > 0 (NaN and -inf give
+// none), nnz[b] their number, and tok / xs / w [B, k] the best k of them in the order (x descending,
+// token ascending) with w = log1pf(xs); slots past the list hold (-1, 0, 0). k in [1, 1024], V >= 1
+// (any size: the row is read from global memory), B >= 1.
+void term_select(const float* xmax, const float* bias, int32_t* tok, float* xs, float* w, int32_t* nnz, int B, int V,
+                 int k, hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

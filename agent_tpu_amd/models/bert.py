@@ -726,6 +726,27 @@ class BertClassifier:
         back = tids.to(torch.int32)[tok.clamp(min=0).long()]
         return torch.where(tok >= 0, back, tok), logit, prob, full[3]
 
+    # ------------------------------------------------------------ learned sparse term weights
+    def term_rows(self, ids: torch.Tensor, lens: torch.Tensor, type_ids: Optional[torch.Tensor] = None
+                  ) -> torch.Tensor:
+        """The MLM transform of every row ``t [B*S, H]`` (bf16 on the GPU): every encoder layer in full with
+        normalised rows, then dense + bias + erf-GELU and the LayerNorm ``mlm_ln_*``."""
+        p = self.p
+        h = self.encode(ids, lens, type_ids, cls_only_last=False)
+        h = ops.linear(h, p["mlm_w"], p["mlm_b"], act="gelu")
+        return ops.layernorm(h, p["mlm_ln_g"], p["mlm_ln_b"], self.cfg.eps)
+
+    def terms(self, ids: torch.Tensor, lens: torch.Tensor, k: int, type_ids: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """SPLADE term weights of single-segment rows: ``(tok [B, k] int32, xs [B, k], w [B, k] fp32, nnz [B] int32)``
+        of :func:`ops.term_select` over ``w[b, v] = log1p(relu(max over live tokens of the MLM logit))``: the
+        transform over all rows, then :func:`ops.term_max` against the tied decoder; no logits tensor."""
+        B, S = ids.shape
+        fi = self.fill_inputs()
+        t = self.term_rows(ids, lens, type_ids)
+        xmax = ops.term_max(t.contiguous(), lens, fi["E"], int(S))
+        return ops.term_select(xmax, fi["bias"], k)
+
     def head(self, h: torch.Tensor, B: int, S: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Pooler + classifier + softmax/top-k (K7) over encoder states ``h``."""
         pooled = self.pooled(h, B, S)

@@ -599,6 +599,8 @@ BATCHED_OPS = {"map_rerank": ("map_rerank", "rerank_batch"), "map_rerank_batch":
                "map_answer": ("map_answer", "answer_batch"), "map_answer_batch": ("map_answer", "answer_batch"),
                "map_tag": ("map_tag", "tag_batch"), "map_tag_batch": ("map_tag", "tag_batch"),
                "map_fill": ("map_fill", "fill_batch"), "map_fill_batch": ("map_fill", "fill_batch"),
+               "map_sparse_embed": ("map_sparse_embed", "sparse_batch"),
+               "map_sparse_embed_batch": ("map_sparse_embed", "sparse_batch"),
                "map_zero_shot": ("map_zero_shot", "zero_shot_batch"),
                "map_zero_shot_batch": ("map_zero_shot", "zero_shot_batch"),
                "map_maxsim": ("map_maxsim", "maxsim_batch"), "map_maxsim_batch": ("map_maxsim", "maxsim_batch")}

@@ -1354,6 +1354,76 @@ class ClassifyEngine:
         tok, prob, pos = self.fill_rows(rows, top_k, mask_token, tids)
         return self.map_fills(tok, prob, pos, rows, mask_token)
 
+    # ------------------------------------------------------------ learned sparse terms (map_sparse_embed)
+    # The staging of embed_texts: per chunk of at most B texts one H2D of the packed texts and one captured
+    # graph per ("sparse", bucket, max_terms) (tokenize, model.terms); the live tokens include [CLS] and [SEP].
+    def _check_sparse_args(self, max_terms) -> int:
+        if isinstance(max_terms, bool) or not isinstance(max_terms, int) or not 1 <= max_terms <= ops.MAX_TERMS:
+            raise ValueError("max_terms must be an int in [1, 1024]")
+        if not self.cfg.mlm_head:
+            raise ValueError(self.FILL_NO_HEAD)
+        return max_terms
+
+    def sparse_rows(self, rows: Sequence, max_terms: int = 256
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The term weights of every text: ``(tok [N, k] int32, xs [N, k], w [N, k] fp32, nnz [N] int32)`` left on
+        the engine's device (a DP caller all-gathers them), ``k = max_terms``: the best ``k`` terms in the order
+        (weight descending, token id ascending), ``(-1, 0, 0)`` past a text's terms; ``nnz`` counts the terms
+        before the cut."""
+        k = self._check_sparse_args(max_terms)
+        N, dev = len(rows), self.device
+        tok = torch.full((N, k), -1, dtype=torch.int32, device=dev)
+        xs = torch.zeros((N, k), dtype=torch.float32, device=dev)
+        w = torch.zeros((N, k), dtype=torch.float32, device=dev)
+        nnz = torch.zeros((N,), dtype=torch.int32, device=dev)
+        for b0 in range(0, N, self.B):
+            chunk = rows[b0:b0 + self.B]
+            text, offs = pack_rows(r[:self.max_row_bytes] if isinstance(r, (bytes, bytearray)) else
+                                   r.encode("utf-8")[:self.max_row_bytes] for r in chunk)
+            n = len(chunk)
+            if dev.type == "cuda":
+                bk = self._stage_texts((text, offs), n)
+
+                def fn():
+                    self._tokenize(self.text[0], self.offs[0], ids=self.ids_s[0], lens=self.lens_s[0], rows=bk)
+                    return self.model.terms(self.ids_s[0][:bk], self.lens_s[0][:bk], k)
+
+                outs = self._replay(("sparse", bk, k), fn, prepare=self.model.fill_inputs)
+            else:
+                ids, lens = self._tokenize(torch.from_numpy(text), torch.from_numpy(offs))
+                outs = self.model.terms(ids, lens, k)
+            for dst, src in zip((tok, xs, w, nnz), outs):
+                dst[b0:b0 + n].copy_(src[:n])  # the bucket's padding rows (empty strings) are dropped here
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()  # the pinned rows are free again
+        return tok, xs, w, nnz
+
+    def map_terms(self, tok: torch.Tensor, w: torch.Tensor, nnz: torch.Tensor, min_weight: float = 0.0
+                  ) -> Tuple[List[Dict[str, object]], List[int]]:
+        """Term rows -> lists on the host: one D2H, then per text ``{"token_ids", "tokens", "weights"}`` (``tokens``
+        from the WordPiece vocabulary, None without one) without the terms below ``min_weight``, and ``nnz``."""
+        N, k = (int(v) for v in tok.shape)
+        both = torch.cat([tok.view(torch.float32).reshape(-1), w.reshape(-1),
+                          nnz.view(torch.float32).reshape(-1)]).cpu()  # one D2H, one sync
+        tok_h = both[:N * k].clone().view(torch.int32).view(N, k)
+        w_h = both[N * k:2 * N * k].view(N, k)
+        nnz_h = both[2 * N * k:].clone().view(torch.int32)
+        names = self.vocab.entries if self.vocab is not None else None
+        terms: List[Dict[str, object]] = []
+        for i in range(N):
+            pairs = [(t, x) for t, x in zip(tok_h[i].tolist(), w_h[i].tolist()) if t >= 0 and x >= min_weight]
+            ids = [t for t, _ in pairs]
+            toks = None if names is None else [names[t].decode("utf-8", "replace") if t < len(names) else None
+                                               for t in ids]
+            terms.append({"token_ids": ids, "tokens": toks, "weights": [x for _, x in pairs]})
+        return terms, nnz_h.tolist()
+
+    def sparse_texts(self, rows: Sequence, max_terms: int = 256, min_weight: float = 0.0
+                     ) -> Tuple[List[Dict[str, object]], List[int]]:
+        """:meth:`sparse_rows`, then :meth:`map_terms`: the term lists of an in-memory list of strings."""
+        tok, _, w, nnz = self.sparse_rows(rows, max_terms)
+        return self.map_terms(tok, w, nnz, min_weight)
+
     def rank_scores(self, scores: torch.Tensor, goff: Sequence[int], top_k: int = 10,
                     activation: str = "none") -> RerankResult:
         """The top ``top_k`` (1..32) of every query's own scores, in the total order (score descending,

@@ -62,6 +62,7 @@ OP_TO_MODULE: Dict[str, str] = {
     "map_answer": "map_answer",
     "map_tag": "map_tag",
     "map_fill": "map_fill",
+    "map_sparse_embed": "map_sparse_embed",
     "map_zero_shot": "map_zero_shot",
     "map_maxsim": "map_maxsim",
     "map_summarize": "map_summarize",
