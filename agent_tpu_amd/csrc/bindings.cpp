@@ -743,6 +743,23 @@ PYBIND11_MODULE(_atpu, m) {
     term_select(P<const float>(xmax), P<const float>(bias), P<int32_t>(tok), P<float>(xs), P<float>(w),
                 P<int32_t>(nnz), B, V, k, S(stream));
   });
+  m.def("postings_count", [](uintptr_t indptr, uintptr_t indices, uintptr_t data, uintptr_t counts, int rows, int V,
+                             int64_t nnz, uintptr_t stream) {
+    postings_count(P<const int64_t>(indptr), P<const int32_t>(indices), P<const float>(data), P<int32_t>(counts), rows,
+                   V, nnz, S(stream));
+  });
+  m.def("postings_fill", [](uintptr_t indptr, uintptr_t indices, uintptr_t data, uintptr_t cursor, uintptr_t out,
+                            int rows, int V, int64_t nnz, int cap, uintptr_t stream) {
+    postings_fill(P<const int64_t>(indptr), P<const int32_t>(indices), P<const float>(data), P<int32_t>(cursor),
+                  P<uint32_t>(out), rows, V, nnz, cap, S(stream));
+  });
+  m.def("sparse_scan_partial", [](uintptr_t postings, uintptr_t offsets, uintptr_t block_start, uintptr_t q_ptr,
+                                  uintptr_t q_tok, uintptr_t q_w, uintptr_t ws, int nq, int N, int V, int64_t total,
+                                  int64_t nterms, int k, int items, uintptr_t stream) {
+    sparse_scan_partial(P<const uint32_t>(postings), P<const int32_t>(offsets), P<const int64_t>(block_start),
+                        P<const int64_t>(q_ptr), P<const int32_t>(q_tok), P<const float>(q_w), P<float>(ws), nq, N, V,
+                        total, nterms, k, items, S(stream));
+  });
   m.def("head_topk", [](uintptr_t pooled, int ldp, uintptr_t Wc, uintptr_t bc, uintptr_t logits, uintptr_t idx,
                         uintptr_t score, int B, int N, int C, int k, uintptr_t stream) {
     classify_head_topk(P<const bf16>(pooled), ldp, P<const bf16>(Wc), P<const float>(bc), P<float>(logits),

@@ -27,7 +27,8 @@ BUILD = REPO / "build" / "obj"
 ARCH = os.environ.get("ATPU_ARCH", "gfx950")
 #: translation units compiled without the packed fp32 VALU instructions (v_pk_add_f32 and its kin): their
 #: independent fp32 add chains are kept as scalar-per-lane adds
-NO_PACKED_FP32 = {"pq_ivf.hip", "sim_refine.hip", "sim_binary.hip", "sparse_head.hip"}
+NO_PACKED_FP32 = {"pq_ivf.hip", "sim_refine.hip", "sim_binary.hip", "sparse_head.hip",
+                  "sparse_index.hip"}
 
 
 def _hipcc() -> str:

@@ -637,6 +637,29 @@ void term_max(const bf16* t, const int32_t* lens, const bf16* E, float* xmax, in
 void term_select(const float* xmax, const float* bias, int32_t* tok, float* xs, float* w, int32_t* nnz, int B, int V,
                  int k, hipStream_t stream);
 
+// Inverted index over sparse term weights (sparse_index.hip). Rows are cut into blocks of kSparseBlockRows; a
+// block's postings are grouped by token, one uint32 word each: low 16 bits = row - block_base, high 16 bits = the
+// fp16 bits of the weight (fp32 rounded to nearest even; a weight that rounds to zero is dropped).
+// postings_count / postings_fill take one block's rows as CSR (indptr [rows + 1] int64 into indices / data
+// [nnz]); count adds into counts [V] (zeroed by the caller); fill takes slots from cursor [V] (the exclusive scan
+// of the counts; left as the inclusive one) and writes the block's words to out [cap]. Token ids in [0, V),
+// weights in (0, 256] and at most kSparseMaxTerms distinct tokens per row are the caller's to check.
+// sparse_scan_partial: score(q, row) = float(sum over shared terms of rint(double(wq) * double(wd) * 2^32)) * 2^-32,
+// the sum an int64 (no order); rows with a positive sum are hits. offsets [nblocks, V + 1] int32 relative to
+// block_start [nblocks + 1] int64; the queries are CSR (q_ptr [nq + 1] int64, q_tok / q_w [nterms], at most
+// kSparseMaxTerms distinct tokens each). Grid (items, nq), items <= min(kSimMaxSplits, nblocks): the sorted top-k
+// (value, row as int bits; empty: -inf, 0x7fffffff) of (query, item) goes to ws [nq, items, k, 2], every slot
+// written, for sim_topk_merge with P = items. k in [1, 32], N < 2^31 - 256. Nothing outside these tensors is touched.
+constexpr int kSparseBlockRows = 8192;
+constexpr int kSparseMaxTerms = 1024;
+void postings_count(const int64_t* indptr, const int32_t* indices, const float* data, int32_t* counts, int rows, int V,
+                    int64_t nnz, hipStream_t stream);
+void postings_fill(const int64_t* indptr, const int32_t* indices, const float* data, int32_t* cursor, uint32_t* out,
+                   int rows, int V, int64_t nnz, int cap, hipStream_t stream);
+void sparse_scan_partial(const uint32_t* postings, const int32_t* offsets, const int64_t* block_start,
+                         const int64_t* q_ptr, const int32_t* q_tok, const float* q_w, float* ws, int nq, int N, int V,
+                         int64_t total, int64_t nterms, int k, int items, hipStream_t stream);
+
 // ------------------------------------------------ classify head + top-k (K7)
 // logits[b, c] = pooled[b] · Wc[c] + bc[c]; probs = softmax(logits);
 // writes top-k (descending prob, ties -> lower index) and the full logits.

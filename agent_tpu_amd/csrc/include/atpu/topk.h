@@ -13,6 +13,40 @@ namespace atpu {
 // (value desc, index asc) ordering
 __device__ __forceinline__ bool better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
 
+// A wave's sorted list of KM <= 64 (value, id) entries in LDS (value in x, the id's bits in y), entry e handled
+// by lane e (sim_binary.hip, sparse_index.hip). Every lane brings C candidates; for each c in turn, the lanes
+// whose candidate beats the list's last entry (the bar) are found by ballot and inserted in ascending lane
+// order by a wave-cooperative sorted insert: lane e recomputes entry e from entries e - 1, e and the candidate.
+// The bar rises with every insert and the ballot is taken again. Whole wave, all lanes; ids are distinct.
+template <int KM, int C>
+__device__ __forceinline__ void wave_list_insert(float2* list, int lane, const float (&v)[C], const int (&id)[C]) {
+  const float2 ent = list[min(lane, KM - 1)];
+  float lv = ent.x;
+  int li = __float_as_int(ent.y);
+  const int below = 4 * max(lane - 1, 0);
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), KM - 1));
+    int bi = __builtin_amdgcn_readlane(li, KM - 1);
+    unsigned long long m = __ballot(better(v[c], id[c], bv, bi));
+    while (m) {
+      const int src = __ffsll(m) - 1;
+      const float cv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[c]), src));
+      const int ci = __builtin_amdgcn_readlane(id[c], src);
+      const float pv = __int_as_float(__builtin_amdgcn_ds_bpermute(below, __float_as_int(lv)));
+      const int pi = __builtin_amdgcn_ds_bpermute(below, li);
+      const bool here = better(cv, ci, lv, li), above = lane > 0 && better(cv, ci, pv, pi);
+      lv = here ? (above ? pv : cv) : lv;
+      li = here ? (above ? pi : ci) : li;
+      bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), KM - 1));
+      bi = __builtin_amdgcn_readlane(li, KM - 1);
+      m &= m - 1;
+      m &= __ballot(better(v[c], id[c], bv, bi));  // the bar rose: some lanes no longer beat it
+    }
+  }
+  if (lane < KM) list[lane] = float2{lv, __int_as_float(li)};
+}
+
 // insert (val, id) into a sorted register list; compile-time indices only
 template <int KM>
 __device__ __forceinline__ void list_insert(float (&tv)[KM], int (&ti)[KM], float val, int id) {

@@ -75,36 +75,6 @@ __global__ __launch_bounds__(kPackThreads) void binary_pack_kernel(const float* 
   }
 }
 
-// the candidates of the lanes that beat the bar go into the (wave, query) list: entry e lives in lane e
-template <int KM>
-__device__ __forceinline__ void ham_insert(float2* list, int lane, const float (&v)[2], const int (&id)[2]) {
-  const float2 ent = list[min(lane, KM - 1)];
-  float lv = ent.x;
-  int li = __float_as_int(ent.y);
-  const int below = 4 * max(lane - 1, 0);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    float bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), KM - 1));
-    int bi = __builtin_amdgcn_readlane(li, KM - 1);
-    unsigned long long m = __ballot(better(v[c], id[c], bv, bi));
-    while (m) {
-      const int src = __ffsll(m) - 1;  // ascending lane = ascending row
-      const float cv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[c]), src));
-      const int ci = __builtin_amdgcn_readlane(id[c], src);
-      const float pv = __int_as_float(__builtin_amdgcn_ds_bpermute(below, __float_as_int(lv)));
-      const int pi = __builtin_amdgcn_ds_bpermute(below, li);
-      const bool here = better(cv, ci, lv, li), above = lane > 0 && better(cv, ci, pv, pi);
-      lv = here ? (above ? pv : cv) : lv;
-      li = here ? (above ? pi : ci) : li;
-      bv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), KM - 1));
-      bi = __builtin_amdgcn_readlane(li, KM - 1);
-      m &= m - 1;
-      m &= __ballot(better(v[c], id[c], bv, bi));  // the bar rose: some lanes no longer beat it
-    }
-  }
-  if (lane < KM) list[lane] = float2{lv, __int_as_float(li)};
-}
-
 template <int WP, int KM>
 __global__ __launch_bounds__(kHamThreads) void hamming_scan_kernel(const uint32_t* __restrict__ qbits,
                                                                    const uint32_t* __restrict__ codes,
@@ -163,7 +133,7 @@ __global__ __launch_bounds__(kHamThreads) void hamming_scan_kernel(const uint32_
       const float bv = bar.x;
       const int bi = __float_as_int(bar.y);
       if (__ballot(better(v[0], id[0], bv, bi) || better(v[1], id[1], bv, bi)) != 0)
-        ham_insert<KM>(wl + qi * KM, lane, v, id);
+        wave_list_insert<KM, 2>(wl + qi * KM, lane, v, id);  // ascending lane = ascending row
     }
   }
   __syncthreads();

@@ -50,6 +50,8 @@ from .tag import (tag_entities, tag_ok, tag_logits_ref, tag_select_ref, tag_grou
 from .fill import (fill_assemble, fill_assemble_ref, mask_gather, mask_gather_ref, vocab_topk, vocab_topk_ok,  # noqa: F401
                    vocab_logits_ref, vocab_select_ref, vocab_topk_splits)
 from .sparse import term_max, term_max_ok, term_max_ref, term_select, term_select_ref, MAX_TERMS  # noqa: F401
+from .sparse_index import (SparseIndex, sparse_index_build, sparse_index_build_ref, sparse_index_cat,  # noqa: F401
+                           sparse_scan_topk, sparse_scan_topk_ref, check_queries)
 from .zeroshot import premise_assemble, premise_assemble_ref, nli_rank, nli_rank_ref  # noqa: F401
 from .head import classify_head_topk  # noqa: F401
 from .reduce import risk_stats, reduce_stats_tensor  # noqa: F401

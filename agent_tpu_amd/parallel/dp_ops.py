@@ -568,6 +568,28 @@ def search_batch_task(payload: Dict[str, Any]) -> Any:
     return ms.search_batch(payload["payloads"], rank, ws)
 
 
+# -------------------------------------------------------- map_sparse_search
+@dp_task("map_sparse_search")
+def sparse_search_task(payload: Dict[str, Any]) -> Any:
+    """One map_sparse_search job: every rank scans its ``split_range`` slice of the rows' inverted index with
+    ``id_base`` = the slice start; the per-rank lists are all-gathered (C2) and merged on rank 0 in the total order
+    (:func:`ops.map_sparse_search.search_rows`). The model is loaded only for the ``queries`` form."""
+    from ops import map_sparse_search as mss
+
+    rank, ws = world()
+    return mss.search_one(payload, rank, ws)
+
+
+@dp_task("map_sparse_search_batch")
+def sparse_search_batch_task(payload: Dict[str, Any]) -> Any:
+    """Several map_sparse_search jobs of one lease (same model, corpus, max_query_terms and query form):
+    :func:`ops.map_sparse_search.search_batch` on every rank."""
+    from ops import map_sparse_search as mss
+
+    rank, ws = world()
+    return mss.search_batch(payload["payloads"], rank, ws)
+
+
 # -------------------------------------------------------------- map_cluster
 @dp_task("map_cluster")
 def cluster_task(payload: Dict[str, Any]) -> Any:

@@ -10,6 +10,9 @@ map_sparse_embed.CONTRACT.md):
 1. one text: ``{"text": "..."}``;
 2. several: ``{"texts": ["...", ...]}``.
 
+``output: "npz"`` with ``output_uri`` writes the rows as a CSR ``.npz`` instead of returning the lists: the corpus
+file of ``map_sparse_search``.
+
 Under ``torchrun`` the texts are split over every GPU of the node, the per-rank term rows are all-gathered and
 rank 0 maps them. Errors are ``ValueError`` s with the fixed messages of :data:`ERRORS`; there is no fallback
 stub.
@@ -17,6 +20,7 @@ stub.
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Dict, List, NamedTuple, Optional
 
 from . import _jobs, register_batch_op, register_op
@@ -35,11 +39,18 @@ ERRORS: Dict[str, str] = {
     "min_weight": "payload.min_weight must be a finite number >= 0",
     "mlm": "model has no MLM head",
 }
+#: the errors of the file output (listed there too)
+OUTPUT_ERRORS: Dict[str, str] = {
+    "output": "payload.output must be 'terms' or 'npz'",
+    "output_uri": "payload.output_uri (a local path) is required for output 'npz'",
+}
 
 
 class Options(NamedTuple):
     max_terms: int
     min_weight: float
+    output: str = "terms"
+    output_uri: Optional[str] = None
 
 
 def options(payload: Dict[str, Any]) -> Options:
@@ -51,7 +62,13 @@ def options(payload: Dict[str, Any]) -> Options:
     mw = 0.0 if mw is None else mw
     if not math.isfinite(mw) or mw < 0:
         raise ValueError(ERRORS["min_weight"])
-    return Options(k, mw)
+    form = payload.get("output", "terms")
+    if form not in ("terms", "npz"):
+        raise ValueError(OUTPUT_ERRORS["output"])
+    uri = payload.get("output_uri")
+    if form == "npz" and (not isinstance(uri, str) or not uri or "://" in uri):
+        raise ValueError(OUTPUT_ERRORS["output_uri"])
+    return Options(k, mw, form, uri if form == "npz" else None)
 
 
 def check_model(h) -> None:
@@ -68,7 +85,16 @@ def result(h, opt: Options, n: int, terms: List[Dict[str, Any]], nnz: List[int],
            "vocab_size": int(h.cfg.vocab_size), "max_terms": opt.max_terms,
            "elapsed_ms": elapsed_ms, "rows_per_sec": rate}
     out.update(extra)
-    out["terms"] = terms
+    if opt.output == "npz":  # the corpus file of map_sparse_search: CSR, fp32, the tokens of a row ascending
+        from agent_tpu_amd.runtime.sparse_index import save_csr
+
+        rows = [sorted(zip(t["token_ids"], t["weights"])) for t in terms]  # min_weight is applied already
+        save_csr(opt.output_uri, _jobs.offsets(rows), [t for r in rows for t, _ in r], [w for r in rows for _, w in r],
+                 (n, int(h.cfg.vocab_size)))
+        out.update(output_uri=opt.output_uri, shape=[n, int(h.cfg.vocab_size)], stored=sum(len(r) for r in rows),
+                   bytes=os.path.getsize(opt.output_uri))
+    else:
+        out["terms"] = terms
     out["nnz"] = [int(c) for c in nnz]
     return out
 
