@@ -425,6 +425,30 @@ PYBIND11_MODULE(_atpu, m) {
       py::arg("q"), py::arg("store"), py::arg("half"), py::arg("row_scale"), py::arg("cand"), py::arg("cand_stride"),
       py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("R"), py::arg("k"), py::arg("P"),
       py::arg("stream"));
+  m.def(
+      "mmr_select",
+      [](uintptr_t cand, uintptr_t rel, uintptr_t store, bool half, uintptr_t row_scale, uintptr_t out_ids,
+         uintptr_t out_rel, uintptr_t out_mmr, int nq, int N, int D, int R, int k, float lam, float mu, int64_t id_base,
+         uintptr_t stream) {
+        mmr_select(P<const int32_t>(cand), P<const float>(rel), P<const void>(store), half, P<const float>(row_scale),
+                   P<int64_t>(out_ids), P<float>(out_rel), P<float>(out_mmr), nq, N, D, R, k, lam, mu, id_base,
+                   S(stream));
+      },
+      "greedy MMR picks over every query's R (16 or 32) candidate rows of an fp32 or fp16 store (device or pinned host "
+      "memory): the Gram matrix and the selection in one kernel",
+      py::arg("cand"), py::arg("rel"), py::arg("store"), py::arg("half"), py::arg("row_scale"), py::arg("out_ids"),
+      py::arg("out_rel"), py::arg("out_mmr"), py::arg("nq"), py::arg("N"), py::arg("D"), py::arg("R"), py::arg("k"),
+      py::arg("lam"), py::arg("mu"), py::arg("id_base"), py::arg("stream"));
+  m.def(
+      "rows_gather",
+      [](uintptr_t ids, uintptr_t store, bool half, uintptr_t row_scale, uintptr_t out, uintptr_t out_scale, int m, int N,
+         int D, int64_t id_base, uintptr_t stream) {
+        rows_gather(P<const int64_t>(ids), P<const void>(store), half, P<const float>(row_scale), P<void>(out),
+                    P<float>(out_scale), m, N, D, id_base, S(stream));
+      },
+      "rows ids - id_base of an fp32 or fp16 store (and their row scales) into a dense buffer; ids outside it give zeros",
+      py::arg("ids"), py::arg("store"), py::arg("half"), py::arg("row_scale"), py::arg("out"), py::arg("out_scale"),
+      py::arg("m"), py::arg("N"), py::arg("D"), py::arg("id_base"), py::arg("stream"));
   m.def("kmeans_shape_ok",&kmeans_shape_ok, "shapes the k-means kernels take", py::arg("D"), py::arg("K"));
   m.def(
       "kmeans_assign",

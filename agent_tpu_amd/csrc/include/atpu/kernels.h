@@ -251,6 +251,24 @@ int refine_chunks(int R, int want);
 void refine_topk_partial(const float* q, const void* store, bool half, const float* row_scale, const int32_t* cand,
                          int cand_stride, float* ws, int nq, int N, int D, int R, int k, int P, hipStream_t stream);
 
+// ---------------------------------------------------------------- diversified results (sim_mmr.hip)
+// mmr_select: greedy maximal-marginal-relevance picks over every query's R candidates, cand [nq, R] (int32 ids into
+// the store, distinct per query; an id outside [0, N) is an empty slot and is never dereferenced) with relevance
+// rel [nq, R]. G[i][j] = the dot product of candidates i and j with sim_topk's bits (store [N, D] fp32, or fp16 (half)
+// with an optional fp32 row_scale [N]: G * (s_i * s_j)); round t picks the arg-max under better() of
+// v_l = rel_l * lam (t = 0) or rel_l * lam - mu * max over the picks j of G[l][j]: three fp32 roundings, no
+// contraction. Pick t goes to out_ids (id_base + row), out_rel and out_mmr [nq, k]; past the live candidates:
+// (id_base + 0x7fffffff, -inf, -inf). The store may be pinned host memory given by its device-visible address.
+// R is 16 or 32, k in [1, R], D % 64 == 0, D in [64, 1024], N < 2^31 - 256. Nothing outside store[0:N],
+// row_scale[0:N] and the R slots of a query is read.
+// rows_gather: out [m, D] (the store's dtype) = store[ids[i] - id_base], out_scale [m] = row_scale[..] when given;
+// an id outside the store gives a zero row and scale 1.
+void mmr_select(const int32_t* cand, const float* rel, const void* store, bool half, const float* row_scale,
+                int64_t* out_ids, float* out_rel, float* out_mmr, int nq, int N, int D, int R, int k, float lam,
+                float mu, int64_t id_base, hipStream_t stream);
+void rows_gather(const int64_t* ids, const void* store, bool half, const float* row_scale, void* out, float* out_scale,
+                 int m, int N, int D, int64_t id_base, hipStream_t stream);
+
 // ---------------------------------------------------------------- binary corpus (sim_binary.hip)
 // A row of D floats as D bits: bit b of word w (uint32) of a row = x[row, 32 w + b] > thr[32 w + b] (a plain
 // comparison: -0.0, +0.0 and NaN give 0 against a zero threshold). W = D / 32, D % 64 == 0, D in [64, 1024].

@@ -30,6 +30,7 @@ from .pq_ivf import (pq_encode_residual, pq_encode_residual_ref, pq_coarse, pq_c
                      sim_topk_ivfpq, sim_topk_ivfpq_ref)
 from .refine import (refine_topk, refine_topk_ref, pq_scan_segments, pq_scan_segments_ref, segment_rows,  # noqa: F401
                      shortlist_rows, candidates_ok)
+from .mmr import mmr_select, mmr_select_ref, mmr_weights, rows_gather, rows_gather_ref  # noqa: F401
 from .binary import (binary_ok, binary_pack, binary_pack_ref, hamming_scan_topk, hamming_scan_topk_ref,  # noqa: F401
                      hamming_scan_segments, hamming_scan_segments_ref, sim_topk_binary, sim_topk_binary_ref,
                      binary_interleave, binary_deinterleave, BinaryCodes)

@@ -242,6 +242,23 @@ def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0,
     return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale)
 
 
+def diversify(scores: torch.Tensor, ids: torch.Tensor, store: torch.Tensor, k: int, lam: float, id_base: int = 0,
+              row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Maximal marginal relevance over every query's candidate list: ``scores`` / ``ids [nq, R]`` as :func:`search`
+    or :func:`merge_topk` leaves them (``R <= 32``, padding ``(-inf, 2^62)``), the ids' rows being
+    ``store[id - id_base]``. -> (ids, scores, mmr) ``[nq, k]`` in pick order on the store's device: ``ops.mmr_select``
+    on the GPU (the candidates' Gram matrix and the greedy selection in one kernel) and its PyTorch twin on a CPU
+    engine. Padding never wins; past the live candidates the entries are ``(2^62, -inf, -inf)``."""
+    from .. import ops
+    from ..ops.search import PAD_ID, _NO_ROW
+
+    dev = store.device
+    ids = ids.to(dev)
+    cand = torch.where(ids == PAD_ID, torch.full_like(ids, _NO_ROW), ids - int(id_base)).to(torch.int32).contiguous()
+    rel = scores.to(device=dev, dtype=torch.float32).contiguous()
+    return ops.mmr_select(rel, cand, store, k, lam, id_base=id_base, row_scale=row_scale)
+
+
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """The best ``k`` columns of every row of ``scores`` / ``ids [nq, m]`` in the (score desc, id asc)
     order: two stable sorts, the minor key first. Padding is ``(-inf, 2^62)`` and sorts last."""

@@ -145,6 +145,15 @@ REFINE_KEYS = ("candidates", "vectors", "store")
 REFINE_VECTORS = ("float16", "float32")
 REFINE_STORES = ("host", "device")
 MAX_REFINE_CANDIDATES = 8192  # 32 * MAX_SPLITS: one list of 32 per segment
+#: those of ``diversify`` (also in the contract)
+DIVERSIFY_ERRORS: Dict[str, str] = {
+    "diversify": ("payload.diversify must be an object with optional 'lambda', a number from 0 to 1, and 'candidates', an "
+                  "integer from max(top_k, 2) to 32"),
+    "diversify_index": "payload.diversify cannot be combined with payload.index",
+    "diversify_compression": "payload.diversify cannot be combined with payload.compression",
+}
+DIVERSIFY_KEYS = ("lambda", "candidates")
+MAX_DIVERSIFY_CANDIDATES = 32  # MAX_TOP_K: the candidates are one sim_topk list
 
 
 class Options(NamedTuple):
@@ -160,6 +169,7 @@ class Options(NamedTuple):
     ivfpq: Optional[tuple] = None  # canonical: (clusters or None, nprobe or None, subvectors, train_rows or None, iterations)
     refine: Optional[tuple] = None  # canonical: (candidates, vectors, store)
     binary: Optional[tuple] = None  # canonical: (threshold,)
+    diversify: Optional[tuple] = None  # canonical: (lambda, candidates)
 
 
 def _number(x: Any) -> bool:
@@ -394,6 +404,22 @@ def parse_refine(payload: Dict[str, Any], opt: Options) -> tuple:
     return R, vectors, store
 
 
+def parse_diversify(payload: Dict[str, Any], opt: Options) -> tuple:
+    """``payload.diversify`` in canonical form, ``(lambda, candidates)``; all of it can be refused without the corpus."""
+    dv = payload["diversify"]
+    if not isinstance(dv, dict) or not set(dv) <= set(DIVERSIFY_KEYS):
+        raise ValueError(DIVERSIFY_ERRORS["diversify"])
+    lam, R = dv.get("lambda", 0.5), dv.get("candidates", MAX_DIVERSIFY_CANDIDATES)
+    if not _number(lam) or not 0 <= lam <= 1 or not isinstance(R, int) or isinstance(R, bool) \
+            or not max(opt.top_k, 2) <= R <= MAX_DIVERSIFY_CANDIDATES:
+        raise ValueError(DIVERSIFY_ERRORS["diversify"])
+    if "index" in payload:  # their rows are not resident in the original order
+        raise ValueError(DIVERSIFY_ERRORS["diversify_index"])
+    if "compression" in payload:
+        raise ValueError(DIVERSIFY_ERRORS["diversify_compression"])
+    return float(lam), R
+
+
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work."""
     top_k = payload.get("top_k", 10)
@@ -420,8 +446,16 @@ def options(payload: Dict[str, Any]) -> Options:
 
 
 def check_payload(payload: Dict[str, Any]) -> Options:
-    """Everything that can be refused without a device or a file: options, then the query and
-    corpus forms."""
+    """Everything that can be refused without a device or a file: :func:`check_forms`, then ``diversify``, so that
+    every other error comes first."""
+    opt = check_forms(payload)
+    if "diversify" in payload:  # a job without one keeps its Options, its code path and its result keys
+        opt = opt._replace(diversify=parse_diversify(payload, opt))
+    return opt
+
+
+def check_forms(payload: Dict[str, Any]) -> Options:
+    """Options, then the query and corpus forms, then the keys that choose a search path."""
     opt = options(payload)
     if "queries" in payload:
         if not isinstance(payload["queries"], list):
@@ -487,7 +521,7 @@ def slice_mask(flt, labels_uri, total: int, s_r: int, n_r: int, device):
 
 
 def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric: str, pooling: str,
-                   rank: int, ws: int, corpus_dtype: str = "float32", flt=None, labels_uri=None):
+                   rank: int, ws: int, corpus_dtype: str = "float32", flt=None, labels_uri=None, diversify=None):
     """Every rank: this rank's slice of the corpus (resident as ``corpus_dtype`` in the ``corpus_uri``
     form) searched for all ``qvecs [nq, dim]`` (host or device fp32, already normalised for
     cosine), the per-rank lists padded to ``top_k``,
@@ -495,7 +529,9 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
     index_cached or None, filter_rows or None) on rank 0, None elsewhere. Local errors are exchanged
     before the collective, so a bad corpus fails every rank together with the single-process message.
     With a filter ``flt`` (canonical form) every rank masks its own slice; the ranks' counts of allowed
-    rows travel with the error exchange, and their sum is ``filter_rows``."""
+    rows travel with the error exchange, and their sum is ``filter_rows``.
+    With ``diversify`` (canonical form) the search runs at ``k = candidates`` and :func:`diversify_lists` picks
+    ``top_k`` of every query's merged list; the tuple gains the picks' ``mmr`` values."""
     import torch
 
     from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
@@ -503,7 +539,10 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
     from agent_tpu_amd.runtime import search as rs
 
     cosine = metric == "cosine"
-    exc, s, i, total, cached, scale, allowed = None, None, None, 0, None, None, 0
+    want = top_k
+    if diversify is not None:  # the candidates: the (filtered) top-R
+        top_k = diversify[1]
+    exc, s, i, total, cached, scale, allowed, vec, s_r = None, None, None, 0, None, None, 0, None, 0
     nq, dim = int(qvecs.shape[0]), int(qvecs.shape[1])
     try:
         if "corpus_uri" in payload:
@@ -540,6 +579,13 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
         extras = exchange_errors(exc, (nq if s is not None else 0, allowed))
         counts, filter_rows = [e[0] for e in extras], sum(e[1] for e in extras)
     s, i = all_gather_rows(s.contiguous(), i.contiguous(), counts=counts)
+    if diversify is not None:  # its own tail, on every rank
+        picks = diversify_lists(s, i, vec, scale, s_r, total, want, diversify, rank, ws)
+        if picks is None:
+            return None
+        kk = min(want, total if filter_rows is None else filter_rows)
+        pi, ps, pm = (t[:, :kk].cpu() for t in picks)
+        return ps, pi, total, cached, filter_rows, pm
     if rank != 0:
         return None
     s, i = s.cpu(), i.cpu()
@@ -549,6 +595,58 @@ def search_queries(h, device, qvecs, payload: Dict[str, Any], top_k: int, metric
         s, i = rs.merge_topk(s, i, top_k)
     kk = min(top_k, total if filter_rows is None else filter_rows)
     return s[:, :kk], i[:, :kk], total, cached, filter_rows
+
+
+def diversify_lists(s, i, vec, scale, s_r: int, total: int, top_k: int, diversify: tuple, rank: int, ws: int):
+    """Every rank, after the all-gather of the ranks' top-``candidates`` lists ``s`` / ``i [ws * nq, R]``: the MMR picks
+    of every query's merged list -> (ids, scores, mmr) ``[nq, top_k]`` on rank 0, None elsewhere. One process selects
+    straight from its resident rows. Under DP every rank holds the gathered lists, so every rank computes the same
+    merged ids; each copies the rows of its own slice into a ``[nq * R, dim]`` buffer (``ops.rows_gather``: zeros for
+    the other slots), the buffers are gathered, and rank 0 takes each slot from its owning rank by select and runs
+    the selection with that buffer as the store and its slot numbers as ids (the slots in ascending id, so that ties
+    break as they do over the ids), then maps the picks back. A row's bits are the same wherever it was gathered, so
+    the result equals the single-process one for every world size."""
+    import torch
+
+    from agent_tpu_amd import ops
+    from agent_tpu_amd.parallel.dp import all_gather_rows, split_range
+    from agent_tpu_amd.runtime import search as rs
+
+    lam, R = diversify
+    if ws == 1:
+        return rs.diversify(s, i, vec, top_k, lam, id_base=s_r, row_scale=scale)
+    nq = s.shape[0] // ws
+    s = s.view(ws, nq, R).permute(1, 0, 2).reshape(nq, ws * R)
+    i = i.view(ws, nq, R).permute(1, 0, 2).reshape(nq, ws * R)
+    s, i = rs.merge_topk(s, i, R)  # [nq, R]: the same on every rank
+    i, by_id = torch.sort(i, dim=1, stable=True)  # ascending id: rank 0's slot numbers then break ties as the ids do
+    s = torch.gather(s, 1, by_id)
+    flat = i.reshape(-1).to(vec.device).contiguous()
+    if vec.shape[0]:
+        rows, sc = ops.rows_gather(flat, vec, id_base=s_r, row_scale=scale)
+    else:  # a rank beyond the corpus owns no slot
+        rows, sc = vec.new_zeros((flat.numel(), vec.shape[1])), None
+    if scale is None:
+        (rows,) = all_gather_rows(rows, counts=[flat.numel()] * ws)
+    else:
+        sc = sc if sc is not None else torch.ones((flat.numel(),), dtype=torch.float32, device=vec.device)
+        rows, sc = all_gather_rows(rows, sc, counts=[flat.numel()] * ws)
+    if rank != 0:
+        return None
+    rows = rows.view(ws, flat.numel(), -1)
+    store, st_scale = rows[0].clone(), (sc.view(ws, -1)[0].clone() if scale is not None else None)
+    for r in range(1, ws):
+        lo, n = split_range(0, total, ws, r)
+        own = (flat >= lo) & (flat < lo + n)
+        store = torch.where(own[:, None], rows[r], store)
+        if st_scale is not None:
+            st_scale = torch.where(own, sc.view(ws, -1)[r], st_scale)
+    slot = torch.arange(flat.numel(), dtype=torch.int64, device=flat.device)
+    cand = torch.where(flat == PAD_ID, flat, slot).view(nq, R)
+    pi, ps, pm = rs.diversify(s, cand, store.contiguous(), top_k, lam, row_scale=st_scale)
+    pad = pi == PAD_ID
+    pi = torch.where(pad, pi, flat[torch.where(pad, torch.zeros_like(pi), pi)]) if flat.numel() else pi
+    return pi, ps, pm
 
 
 def search_queries_ivf(device, qvecs, payload: Dict[str, Any], top_k: int, index: tuple, rank: int, ws: int):
@@ -777,15 +875,18 @@ def embed_queries(h, device, payload: Dict[str, Any], queries: Optional[List[str
 
 def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim: int, cached: Optional[bool],
            ws: int, filter_rows: Optional[int] = None, index_info: Optional[Dict[str, Any]] = None,
-           compression_info: Optional[Dict[str, Any]] = None, refine_info: Optional[Dict[str, Any]] = None
-           ) -> Dict[str, Any]:
+           compression_info: Optional[Dict[str, Any]] = None, refine_info: Optional[Dict[str, Any]] = None,
+           mmr=None) -> Dict[str, Any]:
     """One job's result from its rows of the merged lists (rank 0): the first ``top_k`` entries (with
     a total order a prefix of the top-K is the top-k), then the ``min_score`` cut on the host.
     ``filter_rows``: the corpus rows that passed the job's filter (None: no filter). ``index_info``: the
-    ``index`` key of a job with an index (None: no index); its lists end where the padding begins."""
+    ``index`` key of a job with an index (None: no index); its lists end where the padding begins. ``mmr``: the
+    picks' MMR values of a job with ``diversify`` (None: none); its lists are in pick order, and a prefix of the
+    greedy picks is the shorter job's picks."""
     opt = options(payload)
     kk = min(top_k, total if filter_rows is None else filter_rows)
     ids_l, sc_l = ids[:, :kk].tolist(), scores[:, :kk].tolist()
+    mmr_l = mmr[:, :kk].tolist() if mmr is not None else None
     if index_info is not None:  # a query whose probed clusters hold fewer than top_k rows: a shorter list
         keep = [sum(1 for x in row if x != PAD_ID) for row in ids_l]
         ids_l = [row[:m] for row, m in zip(ids_l, keep)]
@@ -794,6 +895,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
         keep = [[j for j, v in enumerate(row) if v >= opt.min_score] for row in sc_l]
         ids_l = [[row[j] for j in ks] for row, ks in zip(ids_l, keep)]
         sc_l = [[row[j] for j in ks] for row, ks in zip(sc_l, keep)]
+        if mmr_l is not None:
+            mmr_l = [[row[j] for j in ks] for row, ks in zip(mmr_l, keep)]
     n = len(ids_l)
     elapsed_ms, rate = _jobs.timing(payload, n)
     out: Dict[str, Any] = {"ok": True, "op": payload.get("_op", OP_NAME), "query_count": n, "corpus_rows": total,
@@ -818,6 +921,9 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
     if refine_info is not None:
         out["refine"] = dict(refine_info)
     out.update(ids=ids_l, scores=sc_l)
+    if mmr_l is not None:
+        lam, R = parse_diversify(payload, opt)
+        out.update(mmr_scores=mmr_l, diversify={"lambda": lam, "candidates": R})
     return out
 
 
@@ -874,18 +980,21 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info,
                       refine_info=rinfo)
     got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
-                         opt.filter, opt.labels_uri)
+                         opt.filter, opt.labels_uri, opt.diversify)
     if got is None:
         return None
-    s, i, total, cached, filter_rows = got
-    return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, filter_rows)
+    s, i, total, cached, filter_rows = got[:5]
+    return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, filter_rows,
+                  mmr=got[5] if opt.diversify is not None else None)
 
 
 def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional[List[Any]]:
     """The ``queries`` + ``corpus_uri`` jobs of one lease that share (model, pooling, metric, corpus,
     corpus_dtype, canonical filter and its label file, canonical index, canonical compression) as one engine
     call (every rank calls it): one embed of the concatenated queries, one search at the
-    group's largest ``top_k``; each job takes the first ``top_k`` entries of its own rows."""
+    group's largest ``top_k``; each job takes the first ``top_k`` entries of its own rows. A ``diversify`` group
+    (equal canonical ``(lambda, candidates)``) selects once at its largest ``top_k``: a prefix of the greedy picks is
+    the shorter job's picks."""
     out: List[Any] = [None] * len(payloads)
     jobs = []
     for n, p in enumerate(payloads):  # same payloads on every rank: same validation outcome
@@ -896,6 +1005,7 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
     if jobs:
         first = payloads[jobs[0][0]]
         key = jobs[0][1]
+        mmr = None
         h, device = _handle_and_device(first)
         K = max(opt.top_k for _, opt, _ in jobs)
         texts = [t for _, _, ts in jobs for t in ts]
@@ -922,7 +1032,9 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
                 got = None if got is None else got[:4] + (None, None, got[4], got[5])
             else:
                 got = search_queries(h, device, qv, first, K, key.metric, key.pooling, rank, ws, key.corpus_dtype,
-                                     key.filter, key.labels_uri)
+                                     key.filter, key.labels_uri, key.diversify)
+                if got is not None and key.diversify is not None:  # the group's picks at its largest top_k
+                    mmr, got = got[5], got[:5]
                 got = None if got is None else got + (None, None, None)
         except Exception as exc:  # a bad corpus is bad for every job of the group
             for n, _, _ in jobs:
@@ -933,7 +1045,8 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
             pos = 0
             for n, opt, ts in jobs:
                 out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
-                                       int(qv.shape[1]), cached, ws, filter_rows, info, cinfo, rinfo))
+                                       int(qv.shape[1]), cached, ws, filter_rows, info, cinfo, rinfo,
+                                       None if mmr is None else mmr[pos:pos + len(ts)]))
                 pos += len(ts)
     return out if rank == 0 else None
 
@@ -963,6 +1076,8 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
             return group + ("pq",) + opt.compression
         if opt.binary is not None:  # the threshold names the bits; binary jobs never group with PQ jobs
             return group + ("binary",) + opt.binary + ((("refine",) + opt.refine) if opt.refine is not None else ())
+        if opt.diversify is not None:  # the canonical (lambda, candidates): one selection at the group's largest top_k
+            group = group + (("diversify",) + opt.diversify,)
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
 
     return _jobs.lease_batch(payloads, OP_NAME, "map_search_batch", key, run)
