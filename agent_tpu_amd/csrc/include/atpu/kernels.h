@@ -714,4 +714,9 @@ void attention_fwd_strided(const bf16* q, int ldq, const bf16* k, int ldk, const
                            float scale, int causal, hipStream_t stream, const float* bias_dist = nullptr);
 // 1 = long-sequence encoder attention on the double-buffered flash kernel (default), 0 = per-chunk kernel
 int attention_flash_mode(int set);
+// D = 32 (attention_d32.hip; attention_fwd_strided dispatches here): one workgroup per (batch item,
+// head pair, 128 queries); lens mask only, no bias, not causal. Rows and pointers 16-B aligned.
+void attention_d32_fwd_strided(const bf16* q, int ldq, const bf16* k, int ldk, const bf16* v, int ldv, bf16* out,
+                               int ldo, const int32_t* lens, int B, int Sq, int Skv, int H, float scale,
+                               hipStream_t stream);
 }  // namespace atpu

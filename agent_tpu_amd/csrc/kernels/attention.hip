@@ -692,7 +692,12 @@ int attention_flash_mode(int set) {
 void attention_fwd_strided(const bf16* q, int ldq, const bf16* k, int ldk, const bf16* v, int ldv, bf16* out,
                            int ldo, const int32_t* lens, const float* bias, int B, int Sq, int Skv, int H, int D,
                            float scale, int causal, hipStream_t stream, const float* bias_dist) {
-  ATPU_CHECK(D == kD, "attention: head dim must be 64");
+  if (D == 32) {  // MiniLM-class encoders: the head-pair kernels of attention_d32.hip
+    ATPU_CHECK(!causal && !bias && !bias_dist, "attention: head dim 32 is non-causal and takes no bias");
+    attention_d32_fwd_strided(q, ldq, k, ldk, v, ldv, out, ldo, lens, B, Sq, Skv, H, scale, stream);
+    return;
+  }
+  ATPU_CHECK(D == kD, "attention: head dim must be 32 or 64");
   ATPU_CHECK(!(bias && bias_dist), "attention: dense bias and distance bias are exclusive");
   if (bias_dist) {
     ATPU_CHECK(!causal && Sq + Skv - 1 <= kFlashTab, "attention: distance bias needs !causal and Sq + Skv <= 4097");

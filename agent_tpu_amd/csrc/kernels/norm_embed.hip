@@ -177,7 +177,115 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const int32_t* __rest
   }
 }
 
-#define ATPU_NG_DISPATCH(N, CALL)                                    \
+// ---- widths that are odd multiples of 128 (384 for MiniLM-class encoders, 640, 1152) ----
+// Half-wave per row in 128-column groups: 32 lanes x 4 elements (8-byte loads/stores), G =
+// N / 128 groups held in registers, 8 rows per 256-thread block. fp32 two-pass statistics over
+// the half wave, as ln_hw_row. Dead half-waves of the last block compute a valid row and do
+// not store.
+template <int G>
+__device__ __forceinline__ void w128_load(const bf16* p, float (&v)[G * 4], int hl) {
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const bf16x4 x = *reinterpret_cast<const bf16x4*>(p + g * 128 + hl * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[g * 4 + e] = bf2f(x[e]);
+  }
+}
+
+template <int G>
+__device__ __forceinline__ void w128_add(const bf16* p, float (&v)[G * 4], int hl) {
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const bf16x4 x = *reinterpret_cast<const bf16x4*>(p + g * 128 + hl * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[g * 4 + e] += bf2f(x[e]);
+  }
+}
+
+template <int G>
+__device__ __forceinline__ void w128_ln_store(float (&v)[G * 4], const float* gamma, const float* beta, bf16* out,
+                                              bool live, float eps, int hl) {
+  constexpr int N = G * 128;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < G * 4; ++i) s += v[i];
+  const float mean = half_sum(s) * (1.0f / N);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < G * 4; ++i) {
+    const float d = v[i] - mean;
+    q += d * d;
+  }
+  const float rstd = rsqrtf(half_sum(q) * (1.0f / N) + eps);
+  if (!live) return;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int c = g * 128 + hl * 4;
+    const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c);
+    const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + c);
+    bf16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = f2bf((v[g * 4 + e] - mean) * rstd * gm[e] + bt[e]);
+    *reinterpret_cast<bf16x4*>(out + c) = o;
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void layernorm_w128_kernel(const bf16* __restrict__ x, const bf16* __restrict__ res,
+                                                             const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, bf16* __restrict__ out,
+                                                             int rows, float eps) {
+  const int hl = threadIdx.x & 31;
+  const int row = blockIdx.x * 8 + (threadIdx.x >> 5);
+  const bool live = row < rows;
+  const int r = live ? row : rows - 1;
+  constexpr int N = G * 128;
+  float v[G * 4];
+  w128_load<G>(x + (size_t)r * N, v, hl);
+  if (res) w128_add<G>(res + (size_t)r * N, v, hl);
+  w128_ln_store<G>(v, gamma, beta, out + (size_t)r * N, live, eps, hl);
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void embed_ln_w128_kernel(const int32_t* __restrict__ ids,
+                                                            const int32_t* __restrict__ type_ids,
+                                                            const bf16* __restrict__ word,
+                                                            const bf16* __restrict__ pos,
+                                                            const bf16* __restrict__ type,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, bf16* __restrict__ out,
+                                                            int tokens, int S, int vocab, int type_vocab, float eps) {
+  const int hl = threadIdx.x & 31;
+  const int tok = blockIdx.x * 8 + (threadIdx.x >> 5);
+  const bool live = tok < tokens;
+  const int t = live ? tok : tokens - 1;
+  constexpr int N = G * 128;
+  int id = ids[t];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  int tt = type_ids ? type_ids[t] : 0;  // clamped like the word id
+  tt = tt < 0 ? 0 : (tt >= type_vocab ? type_vocab - 1 : tt);
+  float v[G * 4];
+  w128_load<G>(word + (size_t)id * N, v, hl);
+  w128_add<G>(pos + (size_t)(t % S) * N, v, hl);
+  w128_add<G>(type + (size_t)tt * N, v, hl);
+  w128_ln_store<G>(v, gamma, beta, out + (size_t)t * N, live, eps, hl);
+}
+
+// N / 128 odd (an even count is a multiple of 256 and keeps its kernels above)
+#define ATPU_W128_DISPATCH(N, CALL)                                  \
+  switch ((N) / 128) {                                               \
+    case 1: { constexpr int G = 1; CALL; break; }                    \
+    case 3: { constexpr int G = 3; CALL; break; }                    \
+    case 5: { constexpr int G = 5; CALL; break; }                    \
+    case 7: { constexpr int G = 7; CALL; break; }                    \
+    case 9: { constexpr int G = 9; CALL; break; }                    \
+    case 11: { constexpr int G = 11; CALL; break; }                  \
+    case 13: { constexpr int G = 13; CALL; break; }                  \
+    case 15: { constexpr int G = 15; CALL; break; }                  \
+    default: throw std::invalid_argument("atpu: unsupported row width " + std::to_string(N)); \
+  }
+
+#define ATPU_NG_DISPATCH(N, CALL)                                   \
   switch ((N) / 256) {                                               \
     case 1: { constexpr int NG = 1; CALL; break; }                   \
     case 2: { constexpr int NG = 2; CALL; break; }                   \
@@ -203,13 +311,22 @@ __global__ __launch_bounds__(256) void ln_stats_finalize_kernel(const float* __r
 }
 
 inline void check_width(int N) { ATPU_CHECK(N % 256 == 0 && N <= 2048, "row width must be a multiple of 256, <= 2048"); }
+// layernorm_bf16 / embed_layernorm: multiples of 256 on their kernels as before, the other multiples of 128
+// on the *_w128 kernels
+inline void check_width128(int N) { ATPU_CHECK(N > 0 && N % 128 == 0 && N <= 2048, "row width must be a multiple of 128, <= 2048"); }
 
 }  // namespace
 
 void layernorm_bf16(const bf16* x, const bf16* res, const float* gamma, const float* beta, bf16* out, int rows, int N,
                     float eps, hipStream_t stream) {
-  check_width(N);
+  check_width128(N);
   if (rows <= 0) return;
+  if (N % 256 != 0) {
+    ATPU_W128_DISPATCH(N, hipLaunchKernelGGL(layernorm_w128_kernel<G>, dim3((rows + 7) / 8), dim3(256), 0, stream, x,
+                                             res, gamma, beta, out, rows, eps));
+    ATPU_HIP_CHECK(hipGetLastError());
+    return;
+  }
   // ATPU_LN_KERNEL=wave selects the wave-per-row kernel (A/B against the default half-wave kernel).
   static const int mode = [] {
     const char* e = std::getenv("ATPU_LN_KERNEL");
@@ -245,10 +362,17 @@ void rmsnorm_bf16(const bf16* x, const float* gamma, bf16* out, int rows, int N,
 void embed_layernorm(const int32_t* ids, const int32_t* type_ids, const bf16* word, const bf16* pos, const bf16* type,
                      const float* gamma, const float* beta, bf16* out, int B, int S, int N, int vocab, int type_vocab,
                      float eps, hipStream_t stream) {
-  check_width(N);
+  check_width128(N);
   ATPU_CHECK(vocab > 0 && type_vocab > 0, "embedding tables must be non-empty");
   const int tokens = B * S;
   if (tokens <= 0) return;
+  if (N % 256 != 0) {
+    ATPU_W128_DISPATCH(N, hipLaunchKernelGGL(embed_ln_w128_kernel<G>, dim3((tokens + 7) / 8), dim3(256), 0, stream,
+                                             ids, type_ids, word, pos, type, gamma, beta, out, tokens, S, vocab,
+                                             type_vocab, eps));
+    ATPU_HIP_CHECK(hipGetLastError());
+    return;
+  }
   const dim3 grid((tokens + 3) / 4);
   ATPU_NG_DISPATCH(N, hipLaunchKernelGGL(embed_ln_kernel<NG>, grid, dim3(256), 0, stream, ids, type_ids, word, pos,
                                          type, gamma, beta, out, tokens, S, vocab, type_vocab, eps));

@@ -101,6 +101,9 @@ PRESETS: Dict[str, BertConfig] = {
     "bert-base": BertConfig(),
     "bert-large": BertConfig(hidden=1024, layers=24, heads=16, intermediate=4096),
     "bert-tiny": BertConfig(vocab_size=4096, hidden=256, layers=2, heads=4, intermediate=1024, max_positions=512),
+    # MiniLM-class encoders (all-MiniLM-L6/L12, bge-small, e5-small, ms-marco-MiniLM): 12 heads of 32
+    "minilm-l6": BertConfig(hidden=384, layers=6, heads=12, intermediate=1536),
+    "minilm-l12": BertConfig(hidden=384, layers=12, heads=12, intermediate=1536),
 }
 
 
@@ -411,7 +414,7 @@ class BertClassifier:
                     qkv = ops.linear(h0, p[q + "qkv_w"], p[q + "qkv_b"])
                 else:  # consumes LN2_{i-1}(g); fin = its statistics (also the out-proj residual's)
                     qkv = ops.linear_ln(g, f[q + "qkv_w"], f[q + "qkv_b"], in_fin=fin, colsum=f[q + "qkv_c"])
-                ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
+                ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads, head_dim=cfg.head_dim)
             if i == 0:  # the residual h0 is row-major
                 a = ops.linear_ln(ctx, p[q + "o_w"], p[q + "o_b"], residual=h0, part_out=part,
                                   layout=lay(a=ctx_o, c=hid_o))
@@ -450,8 +453,11 @@ class BertClassifier:
         cfg, p, H = self.cfg, self.p, self.cfg.hidden
         q = f"l{cfg.layers - 1}."
         qc = ops.linear(h_cls, p[q + "qkv_w"][:H], p[q + "qkv_b"][:H])
-        ctx = ops.decode_attention(qc, kv[:, :H], kv[:, H:], cfg.heads, S, 1, lens=lens,
-                                   scale=1.0 / math.sqrt(cfg.head_dim))
+        if cfg.head_dim == 64:
+            ctx = ops.decode_attention(qc, kv[:, :H], kv[:, H:], cfg.heads, S, 1, lens=lens,
+                                       scale=1.0 / math.sqrt(cfg.head_dim))
+        else:  # 32-wide heads: the general route of the head-pair attention kernel, one query per row
+            ctx = ops.attention(qc, kv[:, :H], kv[:, H:], lens, B, 1, S, cfg.heads, head_dim=cfg.head_dim)
         h1 = ops.linear(ctx, p[q + "o_w"], p[q + "o_b"], residual=h_cls.contiguous())
         return self._cls_ffn(h1)
 
@@ -505,7 +511,7 @@ class BertClassifier:
         for i in range(last_full):
             q = f"l{i}."
             qkv = self._lin8(h, hq, q + "qkv")
-            ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
+            ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads, head_dim=cfg.head_dim)
             h1 = self._lin8(ctx, None, q + "o", residual=h)
             h1, *h1q = ops.layernorm_quant_i8(h1, p[q + "ln1_g"], p[q + "ln1_b"], cfg.eps)
             f = self._lin8(h1, h1q, q + "f1", act="gelu")
@@ -534,7 +540,7 @@ class BertClassifier:
         for i in range(last_full):
             q = f"l{i}."
             qkv = ops.linear(h, p[q + "qkv_w"], p[q + "qkv_b"])
-            ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads)
+            ctx = ops.attention_packed(qkv, lens, B, S, cfg.heads, head_dim=cfg.head_dim)
             h1 = ops.linear(ctx, p[q + "o_w"], p[q + "o_b"], residual=h)
             h1 = ops.layernorm(h1, p[q + "ln1_g"], p[q + "ln1_b"], cfg.eps)
             f = ops.linear(h1, p[q + "f1_w"], p[q + "f1_b"], act="gelu")

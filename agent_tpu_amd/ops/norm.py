@@ -1,7 +1,9 @@
 """Row normalisation and embedding ops (K2, K6b, T5 RMSNorm).
 
 Native kernels: ``csrc/kernels/norm_embed.hip`` (one wave per row, fp32 stats).
-Row width must be a multiple of 256 (768 / 1024 for BERT, 768 for T5-base).
+Row width must be a multiple of 256 (768 / 1024 for BERT, 768 for T5-base); ``layernorm`` and
+``embed_layernorm`` also take the other multiples of 128 (384 for MiniLM-class encoders) on a
+half-wave-per-row variant with 128-column groups.
 """
 from __future__ import annotations
 

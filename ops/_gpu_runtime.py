@@ -9,7 +9,10 @@ MI355X counterpart of ``/root/reference/ops/_tpu_runtime.py``:
   (ref ``:9-12,39-61``; switching models rebuilt it every time, SURVEY.md
   §2.4.13) with a mutex-guarded LRU of engines resident in HBM.
 
-A "model path" is a BERT preset (``bert-base``, ``bert-large``, ``bert-tiny``),
+A "model path" is a BERT preset (``bert-base``, ``bert-large``, ``bert-tiny``, or the MiniLM-class
+``minilm-l6`` / ``minilm-l12``: hidden 384, 12 heads of 32, which ``map_classify``, ``map_embed``, ``map_rerank``,
+``map_zero_shot`` and ``map_search`` with ``query_texts`` serve; the other head ops run where their head kernel
+takes a width of 384 and fail with its width message where it does not),
 optionally with query options ``bert-base?labels=5&seed=3&batch=512``, or a
 ``.safetensors`` file whose config sits next to it as ``<file>.json``.
 ``?vocab=/abs/vocab.txt[&lowercase=0]`` (any path) or ``"vocab": "vocab.txt"`` in
