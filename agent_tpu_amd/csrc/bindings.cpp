@@ -251,6 +251,40 @@ PYBIND11_MODULE(_atpu, m) {
       "sim_topk_partial over a float16 corpus, the fp32 score times row_scale [N] (0 = none) before the ranking",
       py::arg("q"), py::arg("c"), py::arg("row_scale"), py::arg("ws"), py::arg("nq"), py::arg("N"), py::arg("D"),
       py::arg("k"), py::arg("P"), py::arg("stream"));
+  m.def("sim_topk_wide_splits", &sim_topk_wide_splits,
+        "the split count sim_topk_wide_partial runs: a wanted one (>= 1) up to the limits, or (<= 0) the automatic one",
+        py::arg("N"), py::arg("k"), py::arg("nq"), py::arg("want"));
+  m.def(
+      "sim_topk_wide_partial",
+      [](uintptr_t q, uintptr_t c, uintptr_t buf, uintptr_t part, int nq, int N, int D, int k, int splits,
+         uintptr_t stream) {
+        sim_topk_wide_partial(P<const float>(q), P<const float>(c), P<float>(buf), P<float>(part), nq, N, D, k, splits,
+                              S(stream));
+      },
+      "fp32 similarity GEMM with a deep top-k (k <= 1024) in the epilogue: every wave's sorted top-k (value, row) to "
+      "part [nq, 4 P, k, 2]; buf [ceil(nq / 16), P, 4, 16, 2 K2, 2] holds the candidate buffers",
+      py::arg("q"), py::arg("c"), py::arg("buf"), py::arg("part"), py::arg("nq"), py::arg("N"), py::arg("D"),
+      py::arg("k"), py::arg("P"), py::arg("stream"));
+  m.def(
+      "sim_topk_wide_partial_f16",
+      [](uintptr_t q, uintptr_t c, uintptr_t row_scale, uintptr_t buf, uintptr_t part, int nq, int N, int D, int k,
+         int splits, uintptr_t stream) {
+        sim_topk_wide_partial_f16(P<const float>(q), P<const _Float16>(c), P<const float>(row_scale), P<float>(buf),
+                                  P<float>(part), nq, N, D, k, splits, S(stream));
+      },
+      "sim_topk_wide_partial over a float16 corpus, the fp32 score times row_scale [N] (0 = none) before the ranking",
+      py::arg("q"), py::arg("c"), py::arg("row_scale"), py::arg("buf"), py::arg("part"), py::arg("nq"), py::arg("N"),
+      py::arg("D"), py::arg("k"), py::arg("P"), py::arg("stream"));
+  m.def(
+      "sim_topk_wide_merge",
+      [](uintptr_t part, uintptr_t scores, uintptr_t ids, int nq, int splits, int k, int kk, int64_t id_base,
+         uintptr_t stream) {
+        sim_topk_wide_merge(P<const float>(part), P<float>(scores), P<int64_t>(ids), nq, splits, k, kk, id_base,
+                            S(stream));
+      },
+      "merge of the 4 P per-wave lists of sim_topk_wide_partial in (value desc, row asc) order",
+      py::arg("part"), py::arg("scores"), py::arg("ids"), py::arg("nq"), py::arg("P"), py::arg("k"), py::arg("kk"),
+      py::arg("id_base"), py::arg("stream"));
   m.def("sim_topk_splits_live", &sim_topk_splits_live,
         "the split count the masked sim_topk kernels run for a wanted one, from the live-step count", py::arg("n_live"),
         py::arg("want"));

@@ -157,6 +157,28 @@ void sim_topk_merge(const float* ws, float* scores, int64_t* ids, int nq, int P,
 // Nothing outside c[0:N] and row_scale[0:N] is read.
 void sim_topk_partial_f16(const float* q, const _Float16* c, const float* row_scale, float* ws, int nq, int N, int D,
                           int k, int P, hipStream_t stream);
+// Deep lists (sim_topk_wide.hip): the same exact search for k in [1, 1024], a (query, row) score having the
+// bits sim_topk gives it (fp32 corpus: sim_topk.hip's k order; fp16 corpus with optional row_scale:
+// sim_topk_f16.hip's). P = sim_topk_wide_splits(N, k, nq, wanted): a wanted count >= 1 is kept up to the
+// limits (no empty split, <= kSimMaxSplits, buffers plus partial lists <= kSimWideWsBytes or one split);
+// wanted <= 0 picks the count that leaves every wave at least 4 K2 rows, K2 the power of two >= max(k, 64).
+// nq is not bounded here: one split takes ceil(nq / 16) * 1024 K2 + 32 nq k bytes, so a caller that wants the
+// byte bound kept cuts its query batch to at most kSimWideWsBytes / (64 K2 + 32 k) queries per call.
+// sim_topk_wide_partial* use buf [ceil(nq / 16), P, 4, 16, 2 K2, 2] fp32 as per-wave candidate buffers (contents
+// irrelevant before and after) and leave every wave's sorted top-k (value, row as int bits) in
+// part [nq, 4 P, k, 2] fp32, every slot written, empty ones (-inf, 0x7fffffff). sim_topk_wide_merge reduces
+// part to scores [nq, kk] / ids [nq, kk] = id_base + row in (value desc, row asc) order, 1 <= kk <= k
+// (kk = min(k, N) is the caller's). D % 64 == 0, D in [64, 1024], N < 2^31 - 256; q and c 16-byte aligned.
+// Nothing outside q[0:nq], c[0:N] and row_scale[0:N] is read.
+constexpr int kSimWideMaxK = 1024;
+constexpr int64_t kSimWideWsBytes = int64_t(256) << 20;
+int sim_topk_wide_splits(int N, int k, int nq, int want);
+void sim_topk_wide_partial(const float* q, const float* c, float* buf, float* part, int nq, int N, int D, int k,
+                           int P, hipStream_t stream);
+void sim_topk_wide_partial_f16(const float* q, const _Float16* c, const float* row_scale, float* buf, float* part,
+                               int nq, int N, int D, int k, int P, hipStream_t stream);
+void sim_topk_wide_merge(const float* part, float* scores, int64_t* ids, int nq, int P, int k, int kk,
+                         int64_t id_base, hipStream_t stream);
 // Filtered forms (sim_topk_masked.hip): only the rows whose bit is set in words [ceil(N / 32)] int32
 // (bit b of word w = row 32 w + b; bits at or past N are ignored) enter the lists; live [n_live]
 // int32 lists the non-zero words in ascending order, and only those 32-row steps are read. A score

@@ -20,6 +20,7 @@ from .qkv_attention import qkv_attention, qkv_attention_ok, qkv_head_order  # no
 from .cls_attend import cls_attend, cls_attend_ok, cls_attend_ref, cls_reassoc_weights  # noqa: F401
 from .pool import pool_embed, pool_embed_ok, pool_embed_ref  # noqa: F401
 from .search import sim_topk, sim_topk_ok, sim_topk_ref  # noqa: F401
+from .search import sim_topk_wide, sim_topk_wide_ok  # noqa: F401
 from .search import (RowMask, row_mask_from_ids, row_mask_from_ids_ref, row_mask_from_labels,  # noqa: F401
                      row_mask_from_labels_ref, row_mask_from_bits, row_mask_bits)
 from .search import sim_topk_ivf, sim_topk_ivf_ref, ivf_labels, ivf_plan  # noqa: F401

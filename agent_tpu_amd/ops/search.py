@@ -31,6 +31,10 @@ The filter sits in the kernel's epilogue, and a score keeps the bits it has with
 mapped back, bit for bit, at ``kk = min(k, m.count)`` columns. :func:`row_mask_from_ids` and
 :func:`row_mask_from_labels` build masks on the device (``*_ref``: their PyTorch twins).
 
+:func:`sim_topk_wide` (``csrc/kernels/sim_topk_wide.hip``) is the same exact search for ``k`` up to 1024, with
+the same score bits and the same total order: the register lists of ``sim_topk`` stop at 32 entries, so it
+filters rows against a per-wave threshold and sorts a candidate buffer only when it fills.
+
 :func:`sim_topk_ivf` (``csrc/kernels/sim_topk_ivf.hip``) is the approximate form: the corpus sorted by
 k-means cluster, and every query scored against the rows of the ``nprobe`` clusters nearest to it only, a
 different row set per query. The scores stay exact fp32 dot products with ``sim_topk``'s bits and the ids are
@@ -273,6 +277,72 @@ def sim_topk(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits:
     else:
         nat.sim_topk_partial(ptr(q), ptr(c), ptr(ws), nq, N, D, k, P, stream)
     nat.sim_topk_merge(ptr(ws), ptr(scores), ptr(ids), nq, P, k, kk, int(id_base), stream)
+    return scores, ids
+
+
+# ------------------------------------------------------------------------------------------- deep lists
+WIDE_MAX_K = 1024  # kSimWideMaxK
+WIDE_WS_BYTES = 256 * 2 ** 20  # kSimWideWsBytes: candidate buffers plus partial lists of one call
+
+
+def sim_topk_wide_ok(D: int, k: int) -> bool:
+    """Shapes ``sim_topk_wide`` takes: D a multiple of 64 from 64 to 1024, k in 1..1024."""
+    return D % 64 == 0 and 64 <= D <= 1024 and 1 <= k <= WIDE_MAX_K
+
+
+def sim_topk_wide(q: torch.Tensor, c: torch.Tensor, k: int, id_base: int = 0, splits: Optional[int] = None,
+                  row_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`sim_topk` with lists up to 1024 deep (``csrc/kernels/sim_topk_wide.hip``): (scores ``[nq, kk]`` fp32,
+    ids ``[nq, kk]`` int64), ``kk = min(k, N)``, the exact top-k in the same total order. A (query, row) score has
+    the bits ``sim_topk`` gives it, so for ``k <= 32`` the two agree bit for bit and a deeper list begins with
+    ``sim_topk``'s. Every wave filters the rows it scores against the k-th best it has seen and sorts a buffer
+    of ``2 K2`` candidates (``K2``: the power of two >= max(k, 64)) only when it fills; the result is a pure
+    function of the operands, whatever ``splits`` (None: chosen from N and k), the batch or the run. A batch whose
+    workspace would exceed ``WIDE_WS_BYTES`` at one split (2720 queries at k = 1024) is searched in query chunks
+    of whole 16-query tiles, which changes no bit of the result."""
+    check(q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1], "sim_topk: q [nq, D] and c [N, D]")
+    check(q.dtype == torch.float32 and c.dtype in (torch.float32, torch.float16),
+          "sim_topk: q must be fp32 and c fp32 or fp16")
+    half = c.dtype == torch.float16
+    check(row_scale is None or half, "sim_topk: row_scale needs an fp16 c")
+    if row_scale is not None:
+        check(isinstance(row_scale, torch.Tensor) and row_scale.dtype == torch.float32
+              and row_scale.shape == (c.shape[0],) and row_scale.is_contiguous(),
+              "sim_topk: row_scale must be a contiguous fp32 [N]")
+        same_device(c, row_scale)
+    check(isinstance(k, int) and not isinstance(k, bool), "sim_topk: k must be an int")
+    nq, D = q.shape
+    N = c.shape[0]
+    check(sim_topk_wide_ok(D, k), f"sim_topk_wide: unsupported shape D={D} k={k}")
+    check(1 <= N <= MAX_ROWS, "sim_topk: N must be in [1, 2^31 - 256]")
+    check(q.is_contiguous() and c.is_contiguous(), "sim_topk: contiguous tensors")
+    check(splits is None or (isinstance(splits, int) and 1 <= splits <= MAX_SPLITS),
+          f"sim_topk: splits must be in [1, {MAX_SPLITS}]")
+    same_device(q, c)
+    kk = min(k, N)
+    if nq == 0:
+        return (torch.empty((nq, kk), dtype=torch.float32, device=q.device),
+                torch.empty((nq, kk), dtype=torch.int64, device=q.device))
+    if not q.is_cuda:
+        return sim_topk_ref(q, c, k, id_base, row_scale=row_scale)
+    nat = native()
+    K2 = max(64, 1 << (k - 1).bit_length())
+    scores = torch.empty((nq, kk), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, kk), dtype=torch.int64, device=q.device)
+    stream = launch_stream(q)
+    chunk = WIDE_WS_BYTES // (64 * K2 + 32 * k) // 16 * 16  # queries whose one-split workspace keeps the bound
+    for lo in range(0, nq, chunk):
+        n = min(chunk, nq - lo)
+        qc, sc, ic = q[lo:lo + n], scores[lo:lo + n], ids[lo:lo + n]  # row slices: contiguous, 16-byte aligned
+        P = nat.sim_topk_wide_splits(N, k, n, splits if splits is not None else 0)
+        buf = torch.empty(((n + 15) // 16, P, 4, 16, 2 * K2, 2), dtype=torch.float32, device=q.device)
+        part = torch.empty((n, 4 * P, k, 2), dtype=torch.float32, device=q.device)
+        if half:
+            nat.sim_topk_wide_partial_f16(ptr(qc), ptr(c), ptr(row_scale) if row_scale is not None else 0, ptr(buf),
+                                          ptr(part), n, N, D, k, P, stream)
+        else:
+            nat.sim_topk_wide_partial(ptr(qc), ptr(c), ptr(buf), ptr(part), n, N, D, k, P, stream)
+        nat.sim_topk_wide_merge(ptr(part), ptr(sc), ptr(ic), n, P, k, kk, int(id_base), stream)
     return scores, ids
 
 

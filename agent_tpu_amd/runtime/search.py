@@ -5,7 +5,8 @@ writes with ``output: "npy"``. :func:`load_corpus` memory-maps it, so a DP rank 
 ``[start, start + count)`` slice, widens ``float16`` to fp32 once, normalises the rows on the
 device for the cosine metric (one-time work per index, not the hot path), refuses non-finite
 values, and keeps the loaded slices in a small LRU keyed by the file's identity (a rewritten file
-misses). :func:`search` is ``ops.sim_topk`` on the GPU and its PyTorch twin on a CPU engine.
+misses). :func:`search` is ``ops.sim_topk`` on the GPU (``ops.sim_topk_wide`` for lists deeper than 32) and
+its PyTorch twin on a CPU engine.
 
 With ``dtype="float16"`` the resident rows are fp16 (a ``float16`` file as it is, a ``float32`` file
 rounded to nearest) at half the bytes, and cosine keeps the rows unnormalised beside an fp32
@@ -239,6 +240,8 @@ def search(qvecs: torch.Tensor, corpus: torch.Tensor, k: int, id_base: int = 0,
         return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale, mask=mask)
     if not corpus.is_cuda:
         return ops.sim_topk_ref(q, corpus, k, id_base, row_scale=row_scale)
+    if k > ops.search.MAX_K:  # a deep list (map_search's depth): the buffer-and-sort kernel; k <= 32 stays on the register lists
+        return ops.sim_topk_wide(q, corpus, k, id_base, row_scale=row_scale)
     return ops.sim_topk(q, corpus, k, id_base, row_scale=row_scale)
 
 

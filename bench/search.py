@@ -468,6 +468,52 @@ def ivfpq_bench(a, ops, dev) -> int:
     return 0
 
 
+def depth_bench(a, ops, dev) -> int:
+    """``--depth K [K ...]``: the deep search ``ops.sim_topk_wide`` at these list lengths over random unit rows, fp32
+    or (``--corpus-dtype float16``) fp16. Per (N, queries, depth) three arms alternate for ``--rounds`` rounds on the
+    same tensors: ``sim_topk_wide``, ``torch_matmul_topk`` (``torch.topk(q @ c.T, depth)``, which writes the score
+    matrix; an fp16 corpus is widened once, outside the timing) and ``sim_topk_k32`` (``ops.sim_topk`` at k = 32: the
+    price of depth). The corpus rotates through ``--buffers`` copies as in the plain bench; ``corpus_tbs`` counts
+    the resident corpus bytes once per call. ``ids_equal_torch`` compares the ids with the partner's (random
+    data: no ties expected)."""
+    D = a.dim
+    gen = torch.Generator(device=dev).manual_seed(0)
+    half = a.corpus_dtype == "float16"
+    for N in a.rows:
+        nbuf = a.buffers if N * D * 4 < 512 * 2 ** 20 else 1
+        wide = [torch.nn.functional.normalize(torch.randn(N, D, device=dev, generator=gen), dim=1) for _ in range(nbuf)]
+        cs = [c.half() for c in wide] if half else wide
+        if half:
+            wide = [c.float() for c in cs]
+        for nq in a.queries:
+            q = torch.nn.functional.normalize(torch.randn(nq, D, device=dev, generator=gen), dim=1)
+            for depth in a.depth:
+                arms = {"sim_topk_wide": lambda i: ops.sim_topk_wide(q, cs[i], depth, splits=a.splits or None),
+                        "torch_matmul_topk": lambda i: torch.topk(q @ wide[i].T, depth),
+                        "sim_topk_k32": lambda i: ops.sim_topk(q, cs[i], 32)}
+                same = torch.equal(arms["sim_topk_wide"](0)[1], arms["torch_matmul_topk"](0)[1])
+                for r in range(a.rounds):
+                    for variant, fn in arms.items():
+                        for i in range(max(nbuf, 2)):
+                            fn(i % nbuf)
+                        torch.cuda.synchronize(dev)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for it in range(a.iters):
+                            fn(it % nbuf)
+                        e1.record()
+                        torch.cuda.synchronize(dev)
+                        us = e0.elapsed_time(e1) * 1e3 / a.iters
+                        size = 4 if variant == "torch_matmul_topk" or not half else 2
+                        print(json.dumps({"bench": "search_depth", "variant": variant, "N": N, "queries": nq, "dim": D,
+                                          "depth": depth, "corpus_dtype": a.corpus_dtype, "round": r,
+                                          "us_per_call": round(us, 2), "corpus_tbs": round(N * D * size / us / 1e6, 3),
+                                          "queries_per_sec": round(nq * 1e6 / us, 1), "ids_equal_torch": same}),
+                              flush=True)
+        del cs, wide
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[65536, 1048576])
@@ -498,6 +544,8 @@ def main() -> int:
     ap.add_argument("--refine-store", choices=("host", "device"), default="host")
     ap.add_argument("--pq-train-rows", type=int, default=65536)
     ap.add_argument("--pq-train-iterations", type=int, default=10)
+    ap.add_argument("--depth", type=int, nargs="+", default=None,
+                    help="measure the deep search (sim_topk_wide) at these list lengths instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/search] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -505,6 +553,8 @@ def main() -> int:
     from agent_tpu_amd import ops
 
     dev = torch.device("cuda", 0)
+    if a.depth:
+        return depth_bench(a, ops, dev)
     if a.filter_density:
         return filter_bench(a, ops, dev)
     if a.ivfpq_clusters:

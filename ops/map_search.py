@@ -18,6 +18,9 @@ instead of ``4 dim``, scored from a per-query table of sub-vector dot products (
 are approximate. ``compression`` of type ``binary`` keeps one bit per dimension instead (``agent_tpu_amd/runtime/binary.py``):
 ``dim / 8`` bytes per row, scored by the Hamming distance against the query's bits (``ops.sim_topk_binary``); with
 ``refine`` its shortlist is re-scored exactly.
+``depth`` (33 to 1024, in place of ``top_k``) asks for deep result lists, the input of re-rankers and late-interaction
+scoring: the same exact search through ``ops.sim_topk_wide``, whose selection is a threshold filter and a sorted
+candidate buffer instead of ``sim_topk``'s register lists.
 
 Under ``torchrun`` every rank embeds the queries, searches its slice of the corpus, and rank 0
 merges the per-rank lists in the same total order (score descending, id ascending). Errors are
@@ -154,6 +157,13 @@ DIVERSIFY_ERRORS: Dict[str, str] = {
 }
 DIVERSIFY_KEYS = ("lambda", "candidates")
 MAX_DIVERSIFY_CANDIDATES = 32  # MAX_TOP_K: the candidates are one sim_topk list
+#: those of ``depth`` (also in the contract)
+DEPTH_ERRORS: Dict[str, str] = {
+    "depth": "payload.depth must be an integer from 33 to 1024, given without top_k",
+    "depth_combined": "payload.depth cannot be combined with filter, index, compression, refine or diversify",
+}
+MAX_DEPTH = 1024  # ops.WIDE_MAX_K: the list is one sim_topk_wide call
+DEPTH_EXCLUDES = ("filter", "index", "compression", "refine", "diversify")
 
 
 class Options(NamedTuple):
@@ -170,6 +180,7 @@ class Options(NamedTuple):
     refine: Optional[tuple] = None  # canonical: (candidates, vectors, store)
     binary: Optional[tuple] = None  # canonical: (threshold,)
     diversify: Optional[tuple] = None  # canonical: (lambda, candidates)
+    depth: Optional[int] = None  # the list length of a deep search (33 .. 1024), in place of top_k
 
 
 def _number(x: Any) -> bool:
@@ -420,6 +431,21 @@ def parse_diversify(payload: Dict[str, Any], opt: Options) -> tuple:
     return float(lam), R
 
 
+def parse_depth(payload: Dict[str, Any]) -> int:
+    """``payload.depth``; all of it can be refused without the corpus."""
+    d = payload["depth"]
+    if not isinstance(d, int) or isinstance(d, bool) or not MAX_TOP_K < d <= MAX_DEPTH or "top_k" in payload:
+        raise ValueError(DEPTH_ERRORS["depth"])
+    if any(key in payload for key in DEPTH_EXCLUDES):
+        raise ValueError(DEPTH_ERRORS["depth_combined"])
+    return d
+
+
+def list_length(opt: Options) -> int:
+    """The entries a job asks for per query: its ``depth``, or its ``top_k``."""
+    return opt.top_k if opt.depth is None else opt.depth
+
+
 def options(payload: Dict[str, Any]) -> Options:
     """The validated optional keys; raises the op's ``ValueError`` s before any device work."""
     top_k = payload.get("top_k", 10)
@@ -477,6 +503,8 @@ def check_forms(payload: Dict[str, Any]) -> Options:
             raise ValueError(ERRORS["corpus_texts"])
     else:
         raise ValueError(ERRORS["missing_corpus"])
+    if "depth" in payload:  # a job without one keeps its Options, its code path and its result keys; it joins none
+        return opt._replace(depth=parse_depth(payload))  # of the keys below
     if "filter" in payload:  # a job without one keeps its Options, its code path and its result keys
         flt, labels_uri = parse_filter(payload)
         opt = opt._replace(filter=flt, labels_uri=labels_uri)
@@ -902,6 +930,8 @@ def result(h, scores, ids, payload: Dict[str, Any], top_k: int, total: int, dim:
     out: Dict[str, Any] = {"ok": True, "op": payload.get("_op", OP_NAME), "query_count": n, "corpus_rows": total,
                            "dim": dim, "top_k": top_k, "metric": opt.metric, "elapsed_ms": elapsed_ms,
                            "queries_per_sec": rate}
+    if "depth" in payload:  # a deep search: top_k above is its list length
+        out["depth"] = top_k
     if h is not None:
         out.update(model_path=h.model_path, pooling=opt.pooling)
     if ws > 1:
@@ -979,12 +1009,12 @@ def search_one(payload: Dict[str, Any], rank: int, ws: int) -> Optional[Dict[str
         s, i, total, cached, info, rinfo = got
         return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, compression_info=info,
                       refine_info=rinfo)
-    got = search_queries(h, device, qv, payload, opt.top_k, opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
+    got = search_queries(h, device, qv, payload, list_length(opt), opt.metric, opt.pooling, rank, ws, opt.corpus_dtype,
                          opt.filter, opt.labels_uri, opt.diversify)
     if got is None:
         return None
     s, i, total, cached, filter_rows = got[:5]
-    return result(h, s, i, payload, opt.top_k, total, int(qv.shape[1]), cached, ws, filter_rows,
+    return result(h, s, i, payload, list_length(opt), total, int(qv.shape[1]), cached, ws, filter_rows,
                   mmr=got[5] if opt.diversify is not None else None)
 
 
@@ -1007,7 +1037,7 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
         key = jobs[0][1]
         mmr = None
         h, device = _handle_and_device(first)
-        K = max(opt.top_k for _, opt, _ in jobs)
+        K = max(list_length(opt) for _, opt, _ in jobs)  # a depth group shares its depth
         texts = [t for _, _, ts in jobs for t in ts]
         try:
             if device.type == "cuda":
@@ -1044,7 +1074,7 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
             s, i, total, cached, filter_rows, info, cinfo, rinfo = got
             pos = 0
             for n, opt, ts in jobs:
-                out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], opt.top_k, total,
+                out[n] = ("ok", result(h, s[pos:pos + len(ts)], i[pos:pos + len(ts)], payloads[n], list_length(opt), total,
                                        int(qv.shape[1]), cached, ws, filter_rows, info, cinfo, rinfo,
                                        None if mmr is None else mmr[pos:pos + len(ts)]))
                 pos += len(ts)
@@ -1055,8 +1085,8 @@ def search_batch(payloads: List[Dict[str, Any]], rank: int, ws: int) -> Optional
 def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
     """Batch handler: ``queries`` + ``corpus_uri`` jobs that share (model_path, pooling, metric,
     corpus_uri, corpus_dtype, with a ``filter`` its canonical form and label file, and with an ``index`` its
-    canonical (clusters, train_iterations) and nprobe, and with a ``compression`` its canonical tuple) go to the device
-    together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
+    canonical (clusters, train_iterations) and nprobe, with a ``compression`` its canonical tuple, and with a ``depth``
+    the depth) go to the device together; ``corpus_texts`` jobs, ``query_vectors`` jobs and malformed payloads take the
     single-job path."""
 
     def key(p):
@@ -1076,6 +1106,8 @@ def map_search_batch(payloads: List[Dict[str, Any]]) -> List[Any]:
             return group + ("pq",) + opt.compression
         if opt.binary is not None:  # the threshold names the bits; binary jobs never group with PQ jobs
             return group + ("binary",) + opt.binary + ((("refine",) + opt.refine) if opt.refine is not None else ())
+        if opt.depth is not None:  # jobs of different depths do not share a search
+            return group + (("depth", opt.depth),)
         if opt.diversify is not None:  # the canonical (lambda, candidates): one selection at the group's largest top_k
             group = group + (("diversify",) + opt.diversify,)
         return group if opt.filter is None else group + (opt.filter, opt.labels_uri)  # equal filters share a search
