@@ -720,6 +720,20 @@ PYBIND11_MODULE(_atpu, m) {
                  P<const int32_t>(pidx), P<const int32_t>(qoff), P<const int32_t>(qsel), P<float>(out), Qn, Sq, Pd, T, N, M,
                  E, is_f16, S(stream));
   });
+  m.def("maxsim_index_rc", [](uintptr_t qv, uintptr_t lens_q, uintptr_t codes, uintptr_t cid, uintptr_t centroids,
+                              uintptr_t weights, uintptr_t off, uintptr_t pidx, uintptr_t qoff, uintptr_t qsel,
+                              uintptr_t out, int Qn, int Sq, int Pd, int64_t T, int K, int bits, int N, int M, int E,
+                              uintptr_t stream) {
+    maxsim_index_rc(P<const float>(qv), P<const int32_t>(lens_q), P<const void>(codes), P<const int32_t>(cid),
+                    P<const float>(centroids), P<const float>(weights), P<const int64_t>(off), P<const int32_t>(pidx),
+                    P<const int32_t>(qoff), P<const int32_t>(qsel), P<float>(out), Qn, Sq, Pd, T, K, bits, N, M, E,
+                    S(stream));
+  });
+  m.def("residual_encode", [](uintptr_t x, uintptr_t cid, uintptr_t centroids, uintptr_t cutoffs, uintptr_t codes,
+                              int64_t T, int Pd, int K, int bits, uintptr_t stream) {
+    residual_encode(P<const float>(x), P<const int32_t>(cid), P<const float>(centroids), P<const float>(cutoffs),
+                    P<void>(codes), T, Pd, K, bits, S(stream));
+  });
   m.def("premise_assemble",
         [](uintptr_t ids_t, uintptr_t lens_t, uintptr_t ids_h, uintptr_t lens_h, uintptr_t tidx, uintptr_t hidx,
            uintptr_t ids, uintptr_t type_ids, uintptr_t lens, int rows, int T, int Hn, int Sq, int mh, int cls, int sep,

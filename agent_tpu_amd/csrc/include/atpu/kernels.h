@@ -549,6 +549,21 @@ void maxsim_index(const float* qv, const int32_t* lens_q, const void* tok, const
                   const int32_t* qoff, const int32_t* qsel, float* out, int Qn, int S, int P, int64_t T, int N, int M, int E,
                   int is_f16, hipStream_t stream);
 
+// ---------------------- late interaction over a residual-compressed index (maxsim_residual.hip)
+// maxsim_index on the rows v[t][d] = centroids[clamp(cid[t], 0, K-1)][d] + weights[code(t, d)] (one fp32 add, no
+// renormalisation), decoded into LDS and never stored: the bits of maxsim_index on the decoded fp32 tensor.
+// codes [T, P * bits / 8] uint8 (dimension d in byte d * bits / 8 at bits (d * bits) % 8 .., low bits first),
+// cid [T] int32, centroids [K, P] fp32, weights [2^bits] fp32; the other arguments as maxsim_index.
+// bits in {1, 2, 4}, K in [1, 4096], P % 64 == 0 in [64, 1024]; M == 0: no launch.
+void maxsim_index_rc(const float* qv, const int32_t* lens_q, const void* codes, const int32_t* cid, const float* centroids,
+                     const float* weights, const int64_t* off, const int32_t* pidx, const int32_t* qoff,
+                     const int32_t* qsel, float* out, int Qn, int S, int P, int64_t T, int K, int bits, int N, int M, int E,
+                     hipStream_t stream);
+// codes [T, P * bits / 8] of x [T, P] fp32: code(t, d) = the number of cutoffs [2^bits - 1] strictly below
+// x[t][d] - centroids[clamp(cid[t], 0, K-1)][d] (one fp32 subtraction). T == 0: no launch.
+void residual_encode(const float* x, const int32_t* cid, const float* centroids, const float* cutoffs, void* codes,
+                     int64_t T, int P, int K, int bits, hipStream_t stream);
+
 // ------------------------------------------- zero-shot classification (zeroshot.hip)
 // Premise-first pair rows "atpu-premise v1" (agent_tpu_amd/tokenizer.py premise_rows is the twin): row r
 // with text row t = clamp(tidx[r], 0, T-1) and hypothesis row h = clamp(hidx[r], 0, Hn-1) becomes

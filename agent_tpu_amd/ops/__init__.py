@@ -44,7 +44,8 @@ from .norm import layernorm, rmsnorm, embed_layernorm, embed_gather, embed_pos_l
 from .tokenize import tokenize, tokenize_wordpiece  # noqa: F401
 from .rerank import pair_assemble, pair_assemble_ref, group_topk, group_topk_ref  # noqa: F401
 from .maxsim import (token_unit, token_unit_ref, maxsim, maxsim_ref, maxsim_ok, maxsim_index,  # noqa: F401
-                     maxsim_index_ref)
+                     maxsim_index_ref, maxsim_index_rc, maxsim_index_rc_ref, residual_encode, residual_encode_ref,
+                     residual_decode)
 from .span import span_topk, span_topk_ok, span_topk_ref, span_logits_ref, span_select_ref  # noqa: F401
 from .window import window_assemble, window_assemble_ref, window_best, window_best_ref  # noqa: F401
 from .tag import (tag_entities, tag_ok, tag_logits_ref, tag_select_ref, tag_group_ref, tag_tables,  # noqa: F401

@@ -22,6 +22,9 @@ against the queries ``qsel[qoff[m] .. qoff[m + 1])`` (list form, ``[E]``). fp16 
 which is exact; an fp32 index has the bits of ``maxsim`` on the padded tensors. ``pidx`` is clamped into
 ``[0, N)``, ``qsel`` into ``[0, Qn)``, ``qoff`` into ``[0, E]`` and made monotone, a passage's start into
 ``[0, T)`` and its length ``off[p + 1] - off[p]`` into ``[1, T - start]``.
+
+``maxsim_index_rc`` / ``residual_encode`` / ``residual_decode`` (``csrc/kernels/maxsim_residual.hip``): the same
+score against a residual-compressed index, decoded into LDS while a passage is loaded; see the section below.
 """
 from __future__ import annotations
 
@@ -224,4 +227,127 @@ def maxsim_index(qv: torch.Tensor, lens_q: torch.Tensor, tok: torch.Tensor, off:
         native().maxsim_index(ptr(qv), ptr(lens_q), ptr(tok), ptr(off), ptr(pidx) if pidx is not None else 0,
                               ptr(qoff) if qoff is not None else 0, ptr(qsel) if qsel is not None else 0, ptr(out),
                               Qn, S, P, T, N, M, E, 1 if tok.dtype == torch.float16 else 0, launch_stream(qv))
+    return out
+
+
+# ------------------------------------------------ residual-compressed index (csrc/kernels/maxsim_residual.hip)
+# ColBERTv2's stored form: a token is the id of its nearest centroid and ``bits`` (1, 2 or 4) per dimension,
+#     v[d] = centroids[cid][d] + weights[code[d]]        one fp32 add, NOT renormalised,
+# with ``code[d]`` the number of ``cutoffs`` strictly below ``x[d] - centroids[cid][d]`` (one fp32 subtraction).
+# Dimension ``d``'s code sits in byte ``d * bits / 8`` of the token's ``P * bits / 8`` code bytes at bits
+# ``(d * bits) % 8 .. + bits - 1``, low bits first. ``cid`` is clamped into ``[0, K)`` wherever it is read.
+RESIDUAL_BITS = (1, 2, 4)
+RESIDUAL_MAX_K = 4096  # ops.cluster.kmeans_ok's
+
+
+def _check_residual(name, cid, centroids, table, bits, T, P) -> None:
+    """``table``: the weights ``[2^bits]`` or the cutoffs ``[2^bits - 1]``."""
+    check(bits in RESIDUAL_BITS, f"{name}: bits must be 1, 2 or 4")
+    check(isinstance(cid, torch.Tensor) and cid.dtype == torch.int32 and tuple(cid.shape) == (T,) and cid.is_contiguous(),
+          f"{name}: cid must be a contiguous int32 [T]")
+    check(isinstance(centroids, torch.Tensor) and centroids.dtype == torch.float32 and centroids.dim() == 2
+          and centroids.is_contiguous() and int(centroids.shape[1]) == P and 1 <= int(centroids.shape[0]) <= RESIDUAL_MAX_K,
+          f"{name}: centroids must be a contiguous fp32 [K, P] with K in [1, 4096]")
+    check(isinstance(table, torch.Tensor) and table.dtype == torch.float32 and table.dim() == 1 and table.is_contiguous(),
+          f"{name}: weights and cutoffs must be contiguous fp32 vectors")
+    check(maxsim_ok(P), f"{name}: P must be a multiple of 64 in [64, 1024]")
+
+
+def residual_decode(codes: torch.Tensor, cid: torch.Tensor, centroids: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """The scored values ``[T, P]`` fp32 of a residual index, in plain PyTorch on the tensors' device:
+    ``centroids[clamp(cid)] + weights[code]``, one fp32 add. ``bits`` is ``log2(len(weights))``."""
+    bits = int(weights.numel()).bit_length() - 1
+    T, P = int(codes.shape[0]), int(centroids.shape[1])
+    shifts = torch.arange(0, 8, bits, device=codes.device, dtype=torch.int32)  # low bits first
+    code = (codes.to(torch.int32).unsqueeze(-1) >> shifts) & ((1 << bits) - 1)  # [T, P * bits / 8, 8 / bits]
+    rows = centroids[cid.long().clamp(0, int(centroids.shape[0]) - 1)]
+    return rows + weights[code.reshape(T, P).long()]
+
+
+def residual_encode_ref(x: torch.Tensor, cid: torch.Tensor, centroids: torch.Tensor, cutoffs: torch.Tensor) -> torch.Tensor:
+    """PyTorch twin of :func:`residual_encode` (also the CPU path): ``bucketize`` of the fp32 residual, packed."""
+    bits = int(cutoffs.numel() + 1).bit_length() - 1
+    T, P = x.shape
+    r = x - centroids[cid.long().clamp(0, int(centroids.shape[0]) - 1)]
+    code = torch.bucketize(r, cutoffs).to(torch.int32).view(T, P * bits // 8, 8 // bits)  # cutoffs strictly below
+    shifts = torch.arange(0, 8, bits, device=x.device, dtype=torch.int32)
+    return (code << shifts).sum(-1).to(torch.uint8)
+
+
+def residual_encode(x: torch.Tensor, cid: torch.Tensor, centroids: torch.Tensor, cutoffs: torch.Tensor) -> torch.Tensor:
+    """``codes [T, P * bits / 8]`` uint8 of the contiguous fp32 rows ``x [T, P]`` with the centroid ids ``cid [T]``
+    (int32), ``centroids [K, P]`` and the ascending ``cutoffs [2^bits - 1]`` (fp32), ``bits`` in {1, 2, 4}. An
+    exact integer result; ``x`` must be finite."""
+    check(isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous(),
+          "residual_encode: x must be a contiguous fp32 [T, P]")
+    T, P = x.shape
+    bits = int(cutoffs.numel() + 1).bit_length() - 1 if isinstance(cutoffs, torch.Tensor) else 0
+    _check_residual("residual_encode", cid, centroids, cutoffs, bits, T, P)
+    check(int(cutoffs.numel()) == (1 << bits) - 1, "residual_encode: cutoffs must be [2^bits - 1]")
+    same_device(x, cid, centroids, cutoffs)
+    if not x.is_cuda:
+        return residual_encode_ref(x, cid, centroids, cutoffs)
+    codes = torch.empty((T, P * bits // 8), dtype=torch.uint8, device=x.device)
+    if T:
+        native().residual_encode(ptr(x), ptr(cid), ptr(centroids), ptr(cutoffs), ptr(codes), T, P,
+                                 int(centroids.shape[0]), bits, launch_stream(x))
+    return codes
+
+
+def maxsim_index_rc_ref(qv: torch.Tensor, lens_q: torch.Tensor, codes: torch.Tensor, cid: torch.Tensor,
+                        centroids: torch.Tensor, weights: torch.Tensor, off: torch.Tensor,
+                        pidx: Optional[torch.Tensor] = None, qoff: Optional[torch.Tensor] = None,
+                        qsel: Optional[torch.Tensor] = None, dtype=torch.float32) -> torch.Tensor:
+    """PyTorch twin of :func:`maxsim_index_rc` (also the CPU path): :func:`maxsim_index_ref` over the decoded rows."""
+    return maxsim_index_ref(qv, lens_q, residual_decode(codes, cid, centroids, weights), off, pidx, qoff, qsel, dtype)
+
+
+def maxsim_index_rc(qv: torch.Tensor, lens_q: torch.Tensor, codes: torch.Tensor, cid: torch.Tensor,
+                    centroids: torch.Tensor, weights: torch.Tensor, off: torch.Tensor,
+                    pidx: Optional[torch.Tensor] = None, qoff: Optional[torch.Tensor] = None,
+                    qsel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`maxsim_index` against a residual-compressed index: contiguous ``codes [T, P * bits / 8]`` (uint8),
+    ``cid [T]`` (int32), ``centroids [K, P]`` and ``weights [2^bits]`` (fp32) with ``off [N + 1]``. The passage is
+    decoded into LDS while it is loaded; a score has the bits of ``maxsim_index`` on the fp32 tensor
+    :func:`residual_decode` returns, which is never stored. The other arguments, both forms and every clamp are
+    :func:`maxsim_index`'s."""
+    check(isinstance(qv, torch.Tensor) and qv.dtype == torch.float32 and qv.dim() == 3 and qv.is_contiguous(),
+          "maxsim_index_rc: qv must be a contiguous fp32 [Qn, S, P]")
+    Qn, S, P = qv.shape
+    bits = int(weights.numel()).bit_length() - 1 if isinstance(weights, torch.Tensor) else 0
+    check(isinstance(codes, torch.Tensor) and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous(),
+          "maxsim_index_rc: codes must be a contiguous uint8 [T, P * bits / 8]")
+    T = int(codes.shape[0])
+    _check_residual("maxsim_index_rc", cid, centroids, weights, bits, T, P)
+    check(int(weights.numel()) == 1 << bits and int(codes.shape[1]) * 8 == P * bits,
+          "maxsim_index_rc: weights must be [2^bits] and codes [T, P * bits / 8]")
+    check(isinstance(off, torch.Tensor) and off.dtype == torch.int64 and off.dim() == 1 and off.is_contiguous()
+          and off.numel() >= 2, "maxsim_index_rc: off must be a contiguous int64 [N + 1]")
+    check((qoff is None) == (qsel is None), "maxsim_index_rc: qoff and qsel come together")
+    for t, name in ((lens_q, "lens_q"), (pidx, "pidx"), (qoff, "qoff"), (qsel, "qsel")):
+        check(t is None and name != "lens_q" or isinstance(t, torch.Tensor) and t.dtype == torch.int32
+              and t.dim() == 1 and t.is_contiguous(), f"maxsim_index_rc: {name} must be a contiguous int32 vector")
+    N = int(off.numel()) - 1
+    check(S >= 1 and Qn >= 1 and T >= 1, "maxsim_index_rc: S, Qn and T must be >= 1")
+    check(lens_q.numel() == Qn, "maxsim_index_rc: lens_q must be [Qn]")
+    M = N if pidx is None else int(pidx.numel())
+    E = 0
+    if qoff is not None:
+        check(qoff.numel() == M + 1, "maxsim_index_rc: qoff must be [M + 1]")
+        E = int(qsel.numel())
+    shape = (E,) if qoff is not None else (Qn, M)
+    if out is not None:
+        check(out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous(),
+              "maxsim_index_rc: out must be contiguous fp32 [Qn, M] (all form) or [E] (list form)")
+    same_device(qv, lens_q, codes, cid, centroids, weights, off, pidx, qoff, qsel, out)
+    if not qv.is_cuda:
+        s = maxsim_index_rc_ref(qv, lens_q, codes, cid, centroids, weights, off, pidx, qoff, qsel)
+        return out.copy_(s) if out is not None else s
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=qv.device)
+    if M and out.numel():
+        native().maxsim_index_rc(ptr(qv), ptr(lens_q), ptr(codes), ptr(cid), ptr(centroids), ptr(weights), ptr(off),
+                                 ptr(pidx) if pidx is not None else 0, ptr(qoff) if qoff is not None else 0,
+                                 ptr(qsel) if qsel is not None else 0, ptr(out), Qn, S, P, T, int(centroids.shape[0]),
+                                 bits, N, M, E, launch_stream(qv))
     return out

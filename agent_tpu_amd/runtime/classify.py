@@ -1585,7 +1585,8 @@ class ClassifyEngine:
     # the live rows of every chunk packed with plain PyTorch) and written as an index; a query call then
     # encodes only the queries and scores them against the resident rows with ops.maxsim_index: one
     # all-form launch over the rank's slice, or with per-query candidate lists one list-form launch over
-    # the passage-major work list that PyTorch ops on the device build from them.
+    # the passage-major work list that PyTorch ops on the device build from them. A residual-compressed
+    # index (runtime.maxsim_residual.ResidualIndex) takes the same two launches of ops.maxsim_index_rc.
     def _check_late(self, Q: int = 0) -> None:
         if not ops.maxsim_ok(self.late_dim):
             raise ValueError("token vectors must have a width that is a multiple of 64 in [64, 1024]")
@@ -1626,15 +1627,22 @@ class ClassifyEngine:
 
     def maxsim_index_scores(self, queries: Sequence, index, candidates: Optional[Sequence[Sequence[int]]] = None
                             ) -> torch.Tensor:
-        """Late-interaction scores of the queries against a resident index (``runtime.maxsim_index.TokenIndex``,
-        a rank's slice), fp32 on the engine's device. Without ``candidates``: ``[Q, index.count]``, every query
-        against every passage of the slice, one all-form launch. With ``candidates`` (one list of passage ids
+        """Late-interaction scores of the queries against a resident index (``runtime.maxsim_index.TokenIndex`` or
+        ``runtime.maxsim_residual.ResidualIndex``, a rank's slice), fp32 on the engine's device. Without
+        ``candidates``: ``[Q, index.count]``, every query against every passage of the slice, one all-form launch. With ``candidates`` (one list of passage ids
         of the file per query): ``[Q, C]``, ``C`` the longest list, entry ``[q, j]`` the score of
         ``candidates[q][j]`` when that passage is in the slice and ``-inf`` when it is not (or past the list's
         end): one list-form launch. ``self.maxsim_lens_q`` as in :meth:`maxsim_scores`."""
         Q, P, dev = len(queries), self.late_dim, self.device
         self._check_late(Q)
-        if int(index.tokens.shape[1]) != P:
+        from .maxsim_residual import ResidualIndex
+
+        if isinstance(index, ResidualIndex):
+            width, rows = int(index.centroids.shape[1]), (index.codes, index.cids, index.centroids, index.weights)
+            score = ops.maxsim_index_rc
+        else:
+            width, rows, score = int(index.tokens.shape[1]), (index.tokens,), ops.maxsim_index
+        if width != P:
             raise ValueError("index width is not the model's token-vector width")
         if candidates is not None and len(candidates) != Q:
             raise ValueError("candidates must be one list per query")
@@ -1642,13 +1650,13 @@ class ClassifyEngine:
         if candidates is None:
             if Q == 0 or index.count == 0:
                 return torch.empty((Q, index.count), dtype=torch.float32, device=dev)
-            return ops.maxsim_index(qv, lens_q, index.tokens, index.offsets)
+            return score(qv, lens_q, *rows, index.offsets)
         out = torch.full((Q, max([len(c) for c in candidates], default=0)), float("-inf"), dtype=torch.float32, device=dev)
         if Q == 0 or index.count == 0 or out.numel() == 0:
             return out
         pidx, qoff, qsel, col = self._candidate_entries(candidates, index)
         if qsel.numel():
-            sc = ops.maxsim_index(qv, lens_q, index.tokens, index.offsets, pidx, qoff, qsel)
+            sc = score(qv, lens_q, *rows, index.offsets, pidx, qoff, qsel)
             out[qsel.to(torch.int64), col] = sc
         return out
 

@@ -20,6 +20,13 @@ tokens) at 1 and 32 queries x 1024 and 32 768 passages, against ``ops.maxsim`` o
 same values, outputs compared (fp32: bit for bit). FLOPs count live tokens only. End-to-end part:
 ``maxsim_index_rank`` over an index that ``maxsim_build`` made from 1024 synthetic passages, against
 ``maxsim_rank`` on the same strings in the shared form.
+
+``--mode index --index-compression residual --bits B``: the residual-compressed index on the same SYNTHETIC
+vectors. Built as the op builds it (``runtime.maxsim_residual.compress``: k-means, quantiles, ``residual_encode``,
+each timed), then ``ops.maxsim_index_rc`` against ``ops.maxsim_index`` on the fp16 index of the same passages,
+alternating; resident bytes against fp16; the largest score difference and the top-10 overlap against the fp32
+index. Random unit rows have no cluster structure: the quality figures say nothing about a trained ColBERT
+checkpoint.
 """
 from __future__ import annotations
 
@@ -267,6 +274,76 @@ def index_mode(a, dev) -> None:
     }), flush=True)
 
 
+def residual_index_mode(a, dev) -> None:
+    from agent_tpu_amd import ops
+    from agent_tpu_amd.runtime import cluster, maxsim_residual as mr
+
+    S, P, K = a.seq_len, a.late, a.centroids
+    for N in (1024, 32768):
+        g = torch.Generator().manual_seed(P + N)
+        lens = torch.randint(40, 129, (N,), generator=g)
+        off = torch.zeros(N + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(lens, 0)
+        T = int(off[-1])
+        tok32 = torch.nn.functional.normalize(torch.randn(T, P, generator=g), dim=-1).to(dev)
+        tok16, off_d = tok32.half(), off.to(dev)
+
+        def stage(fn):  # wall clock of one build stage, the device synchronized before and after
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize(dev)
+            return out, round((time.perf_counter() - t0) * 1000.0, 2)
+
+        # runtime.maxsim_residual.compress, stage by stage
+        km, t_km = stage(lambda: cluster.kmeans(tok32, K, "cosine", seed=0, max_iter=8))
+        cent = km.centroids.contiguous()
+        cids = ops.kmeans_assign(tok32, cent)[0]
+        n = min(T, mr.SAMPLE_ROWS)
+        pick = (torch.arange(n, dtype=torch.int64) * T // n).to(dev)
+        steps = torch.arange(2 ** a.bits, dtype=torch.float32, device=dev)
+        res = (tok32[pick] - cent[cids[pick].long()]).reshape(-1)
+        (cuts, w), t_q = stage(lambda: (torch.quantile(res, steps[1:] / 2 ** a.bits).contiguous(),
+                                        torch.quantile(res, (steps + 0.5) / 2 ** a.bits).contiguous()))
+        codes, t_enc = stage(lambda: ops.residual_encode(tok32, cids, cent, cuts))
+        build = {"kmeans_ms": t_km, "quantiles_ms": t_q, "encode_ms": t_enc}
+        rc = {"codes": codes, "cids": cids, "centroids": cent, "weights": w, "iterations": km.iterations}
+        rows = (rc["codes"], rc["cids"], rc["centroids"], rc["weights"])
+        rc_bytes = sum(t.numel() * t.element_size() for t in rows)
+        for Qn in (1, 32):
+            qv = torch.nn.functional.normalize(torch.randn(Qn, S, P, generator=g), dim=-1).to(dev)
+            lens_q = torch.full((Qn,), 32, dtype=torch.int32, device=dev)
+            out_r, out_h = torch.empty((Qn, N), device=dev), torch.empty((Qn, N), device=dev)
+            frc = lambda: ops.maxsim_index_rc(qv, lens_q, *rows, off_d, out=out_r)  # noqa: E731
+            f16 = lambda: ops.maxsim_index(qv, lens_q, tok16, off_d, out=out_h)  # noqa: E731
+            want = ops.maxsim_index(qv, lens_q, tok32, off_d)
+            got = frc().clone()
+            k = min(10, N)
+            top_w, top_g = want.topk(k, dim=1).indices, got.topk(k, dim=1).indices
+            overlap = sum(len(set(x) & set(y)) for x, y in zip(top_w.tolist(), top_g.tolist())) / (Qn * k)
+            fns = (frc, f16)
+            reps = [max(3, int(a.window_ms / _device_ms(f, 3))) for f in fns]
+            times = [[], []]
+            for _ in range(a.rounds):
+                for i, f in enumerate(fns):
+                    times[i].append(_device_ms(f, reps[i]))
+            flops = 2.0 * 32 * P * T * Qn
+            mr_, mh = min(times[0]), min(times[1])
+            print(json.dumps({
+                "metric": f"maxsim_index_rc kernel (synthetic index, residual{a.bits}) P={P} Qn={Qn} N={N} on 1 MI355X",
+                "unit": "ms", "higher_is_better": False, "value": round(mr_, 4), "index_rc_ms": [round(t, 4) for t in times[0]],
+                "index_f16_ms": [round(t, 4) for t in times[1]], "rc_over_f16": round(mr_ / mh, 3),
+                "rc_code_gbps": round(rc["codes"].numel() / mr_ / 1e6, 2), "rc_live_tflops": round(flops / mr_ / 1e9, 2),
+                "f16_live_tflops": round(flops / mh / 1e9, 2), "resident_bytes": {"residual": rc_bytes, "f16": T * P * 2},
+                "f16_over_residual_bytes": round(T * P * 2 / rc_bytes, 2), "max_abs_diff_to_f32": (got - want).abs().max().item(),
+                "top10_overlap_with_f32": round(overlap, 4), "build": build,
+                "config": {"synthetic": True, "quality_is_of_random_unit_rows": True, "S": S, "P": P, "Qn": Qn, "N": N, "T": T,
+                           "bits": a.bits, "centroids": K, "kmeans_iterations": rc["iterations"], "passage_lens": "uniform 40..128",
+                           "len_q": 32, "reps": reps, "rounds": a.rounds},
+            }), flush=True)
+        del tok32, tok16, rc, rows
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("kernel", "pairs", "shared", "index"), default="kernel")
@@ -285,6 +362,9 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--window-ms", type=float, default=250.0, help="kernel mode: device time per timed window")
+    ap.add_argument("--index-compression", choices=("none", "residual"), default="none", help="index mode")
+    ap.add_argument("--bits", type=int, choices=(1, 2, 4), default=2, help="index mode, residual compression")
+    ap.add_argument("--centroids", type=int, default=1024, help="index mode, residual compression")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("[bench/maxsim] needs a ROCm GPU", file=sys.stderr, flush=True)
@@ -292,7 +372,7 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if a.mode == "index":
-        index_mode(a, dev)
+        residual_index_mode(a, dev) if a.index_compression == "residual" else index_mode(a, dev)
     else:
         kernel_mode(a, dev) if a.mode == "kernel" else engine_mode(a, dev)
     return 0

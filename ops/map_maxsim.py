@@ -17,6 +17,10 @@ passages go through the encoder once and a query call encodes only the queries:
 5. index: ``{"queries": [...], "index_uri": path}`` ranks every query against the whole index, or with
    ``"candidates": [[id, ...], ...]`` against its own list of passage ids.
 
+``index_out`` may ask for ColBERTv2's residual compression instead of a ``dtype``: ``"compression": {"type":
+"residual", "bits": 2, "centroids": K, "iterations": 8}`` (``agent_tpu_amd/runtime/maxsim_residual.py``). The same
+``index_uri`` queries it; the kernel decodes each passage while it loads it on chip.
+
 Under ``torchrun`` the passages are split over every GPU of the node (every rank encodes all queries), the
 per-rank scores are all-gathered and rank 0 ranks them; a score depends on its own two texts only, so the
 results are bit-identical for every world size. Errors are ``ValueError`` s with the fixed messages of
@@ -70,6 +74,19 @@ INDEX_ERRORS: Dict[str, str] = {
     "index_too_large": "index slice exceeds SEARCH_INDEX_MAX_GB",
 }
 INDEX_DTYPES = ("float16", "float32")
+
+#: those of a residual-compressed index (also in the contract); the two dicts above keep exactly their keys
+RESIDUAL_ERRORS: Dict[str, str] = {
+    "compression": ('payload.index_out.compression must be {"type": "residual", "centroids": an integer in [1, 4096], '
+                    '"bits": 1, 2 or 4 (default 2), "iterations": an integer in [1, 100] (default 8)}, without a '
+                    '"dtype" beside it'),
+    "compression_rows": "payload.index_out.compression needs at least as many token rows as centroids",
+    "residual_file": "a 2-D uint8 index_uri is a residual index: it needs <name>.cids.npy (1-D int32, one id per "
+                     "token row), <name>.centroids.npy (2-D float32 [K, P], K in [1, 4096]) and <name>.weights.npy "
+                     "(1-D float32 of 2, 4 or 16 values) next to it, and P * bits / 8 code columns",
+    "residual_nonfinite": "residual index centroids or weights hold non-finite values",
+    "index_too_large": INDEX_ERRORS["index_too_large"],
+}
 PAD_ID = 2 ** 62  # id of the (-inf) padding of a rank's list that is shorter than top_k (merge_topk's)
 
 
@@ -97,7 +114,7 @@ def options(payload: Dict[str, Any]) -> Options:
 
 def check_form(payload: Dict[str, Any]) -> Tuple[str, List[str], Any]:
     """``("pairs", queries, passages per query)``, ``("shared", queries, passages)``, ``("build", [], (passages,
-    uri, dtype))`` or ``("index", queries, (uri, candidates or None))``."""
+    uri, dtype, compression or None))`` or ``("index", queries, (uri, candidates or None))``."""
     if "index_out" in payload:
         return _check_build(payload)
     if "index_uri" in payload:
@@ -116,13 +133,28 @@ def check_form(payload: Dict[str, Any]) -> Tuple[str, List[str], Any]:
 
 def _check_build(payload: Dict[str, Any]) -> Tuple[str, List[str], Any]:
     spec, passages = payload["index_out"], payload.get("passages")
-    if (not isinstance(spec, dict) or set(spec) - {"uri", "dtype"} or not isinstance(spec.get("uri"), str)
+    if (not isinstance(spec, dict) or set(spec) - {"uri", "dtype", "compression"} or not isinstance(spec.get("uri"), str)
             or not spec["uri"] or ("://" in spec["uri"] and not spec["uri"].startswith("file://"))
             or spec.get("dtype", "float16") not in INDEX_DTYPES
             or any(k in payload for k in ("query", "queries", "shared_passages", "index_uri", "candidates"))
             or not isinstance(passages, list) or not all(isinstance(p, str) for p in passages)):
         raise ValueError(INDEX_ERRORS["index_out"])
-    return "build", [], (list(passages), spec["uri"], spec.get("dtype", "float16"))
+    return "build", [], (list(passages), spec["uri"], spec.get("dtype", "float16"), _check_compression(spec))
+
+
+def _check_compression(spec: Dict[str, Any]) -> Optional[Dict[str, int]]:
+    """``{"bits", "centroids", "iterations"}`` of ``index_out.compression``, or None without the key."""
+    if "compression" not in spec:
+        return None
+    c = spec["compression"]
+    if not isinstance(c, dict) or set(c) - {"type", "bits", "centroids", "iterations"} or c.get("type") != "residual" \
+            or "dtype" in spec:
+        raise ValueError(RESIDUAL_ERRORS["compression"])
+    out = {"bits": c.get("bits", 2), "centroids": c.get("centroids"), "iterations": c.get("iterations", 8)}
+    if not all(is_int(v) for v in out.values()) or out["bits"] not in (1, 2, 4) or not 1 <= out["centroids"] <= 4096 \
+            or not 1 <= out["iterations"] <= 100:
+        raise ValueError(RESIDUAL_ERRORS["compression"])
+    return out
 
 
 def _check_index(payload: Dict[str, Any]) -> Tuple[str, List[str], Any]:
@@ -242,11 +274,12 @@ def _shared_job(h, job, payload, rank: int, ws: int):
 
 def _build_job(h, job, payload, rank: int, ws: int):
     """One build job: the passages split contiguously over the DP ranks, the packed rows all-gathered in rank
-    order and then the lengths; rank 0 writes both files."""
+    order and then the lengths; rank 0 writes the files, after compressing the gathered rows when
+    ``index_out.compression`` asks for it (one process trains and encodes: no collective is added)."""
     from agent_tpu_amd.parallel.dp import all_gather_rows
     from agent_tpu_amd.runtime import maxsim_index as mi
 
-    passages, uri, dtype = job[4]
+    passages, uri, dtype, comp = job[4]
     box = {}
 
     def compute(s_r, n_r):
@@ -257,7 +290,14 @@ def _build_job(h, job, payload, rank: int, ws: int):
     (lens,) = all_gather_rows(box["lens"])
     if rank != 0:
         return None
-    info = mi.write_index(uri, tok, lens, dtype)
+    if comp is None:
+        info = mi.write_index(uri, tok, lens, dtype)
+    else:
+        from agent_tpu_amd.runtime import maxsim_residual as mr
+
+        if int(tok.shape[0]) < comp["centroids"]:
+            raise ValueError(RESIDUAL_ERRORS["compression_rows"])
+        info = mr.write_index(uri, mr.compress(tok.contiguous(), comp["centroids"], comp["bits"], comp["iterations"]), lens)
     elapsed_ms, rate = _jobs.timing(payload, len(passages))
     out = {"ok": True, "op": payload.get("_op", OP_NAME), "model_path": h.model_path, "form": "build",
            "elapsed_ms": elapsed_ms, "passages_per_sec": rate}
@@ -271,7 +311,10 @@ def _open_index(h, uri, rank: int, ws: int):
     """This rank's contiguous share of the index's passages, resident on the engine's device."""
     from agent_tpu_amd.parallel.dp import split_range
     from agent_tpu_amd.runtime import maxsim_index as mi
+    from agent_tpu_amd.runtime import maxsim_residual as mr
 
+    if mr.is_residual(uri):  # a 2-D uint8 main file; anything else is the float loader's, errors included
+        mi = mr
     total, _, dim, _ = mi.index_shape(uri)
     if dim != h.engine.late_dim:
         raise ValueError(INDEX_ERRORS["index_dim"])
